@@ -19,8 +19,12 @@ Multi-GPU: ONE clip, strong scaling (the metric is "24f x 512^2 at 1/2/4/8 MI355
   --parallel cfg | replicas  CFG pairs x N/2 clips, or one independent clip per GPU (weak scaling, no data-path collective)
 value = clips * steps / max-over-ranks time.  `comm` in the JSON = data-path exchanges per step of rank 0.
 
-Prints ONE JSON line on rank 0 with `roofline` (the device kernel with the largest share of GPU time, HIP-event timed
-on the launch stream) and `cpu_baseline` (the CPU oracle on a bounded sample, rank 0, N = 1).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports them; everything else is
+measured only with `--full`: `roofline` / `kernels` / `kernel_families` (a second, HIP-event-instrumented pass of the same steps),
+`cpu_baseline` (the CPU oracle on a bounded sample, rank 0, N = 1), the exchanges' stream-held times of the multi-GPU modes
+(two more untimed steps), the per-iteration split of --null-text and the kernel families of --vae-decode.
+`--dump-outputs DIR` writes what the timed path returned at its last timed step as DIR/<name>.npy (float32; seeded inputs, so two
+builds can be compared output for output).
 `--emulate` (test plumbing only) runs the product host code on tests/emu_ops.py (torch CPU, gloo) at tiny shapes.
 """
 from __future__ import annotations
@@ -53,7 +57,7 @@ def parse_args():
     ap.add_argument("--latent", type=int, default=64, help="latent height = width (image size / 8)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", choices=["sample", "full", "off"], default="sample",
-                    help="'sample' (default): the CPU oracle timed on ONE step at BASELINE configs[0] (bounded, ~1 min) next to the committed full-config measurement "
+                    help="'sample' (default; measured with --full only): the CPU oracle timed on ONE step at BASELINE configs[0] (bounded, ~1 min) next to the committed full-config measurement "
                          "(profiles/cpu_baseline_full.json); 'full': time ONE oracle step at the bench workload itself (24 f x 64x64 latents: minutes to a quarter of an hour of host "
                          "time, no GPU involved), print it as one JSON line and exit -- run once per round on the GPU box, commit the line as profiles/cpu_baseline_full.json")
     ap.add_argument("--single-branch", action="store_true",
@@ -64,7 +68,7 @@ def parse_args():
     ap.add_argument("--shard-exchange", choices=["lean", "gather"], default="lean",
                     help="frame sharding A/B: 'lean' = frame<->pixel all-to-all for temporal attention + two-frame halos for the adapter (default); "
                          "'gather' = the K|V all-gathers BASELINE configs[3] names")
-    ap.add_argument("--shapes", action="store_true", help="print the GEMM shapes with the largest time share to stderr")
+    ap.add_argument("--shapes", action="store_true", help="print the GEMM shapes with the largest time share to stderr (from the --full roofline pass)")
     ap.add_argument("--editors", choices=["active", "inactive"], default="active",
                     help="secondary measurement: 'inactive' times the un-edited step (steps 0-3 of a 50-step run); the headline metric is 'active'")
     ap.add_argument("--inversion", action="store_true",
@@ -100,7 +104,44 @@ def parse_args():
     ap.add_argument("--zero-tconv", action="store_true",
                     help="secondary measurement: UNet TemporalConv weights exactly zero, as in real checkpoints (resnet_2d.py:15-16) -> the launch is skipped")
     ap.add_argument("--emulate", action="store_true", help="test plumbing: torch-CPU emulation of the C ABI (tests/emu_ops.py), gloo backend")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline / per-kernel pass, the CPU baseline, the exchanges' stream-held "
+                         "times (multi-GPU), the per-iteration split of --null-text, the kernel families of --vae-decode.  Off by default: a plain run "
+                         "only sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned at its last step as DIR/<name>.npy (float32; at most 64 MB in all, "
+                         "larger outputs as a fixed seeded sample).  Multi-process runs: one file per rank, <name>.rank<r>.npy")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1):
+    """Write {name: tensor | array} as out_dir/<name>.npy in float32.  If the arrays hold more than DUMP_LIMIT_BYTES in all, each is replaced by the
+    same fixed, seeded sample of its flattened elements (a share of the limit proportional to its size), so that two runs stay comparable."""
+    import numpy as np
+    out = {}
+    for k, v in arrays.items():
+        if hasattr(v, "detach"):
+            v = v.detach().float().cpu().numpy()
+        out[k] = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
+    total = sum(a.size for a in out.values())
+    budget = DUMP_LIMIT_BYTES // 4 - 1024 * len(out)     # float32 elements, less room for the .npy headers
+    if total > budget:
+        for k, a in out.items():
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=max(1, a.size * budget // total), replace=False))
+            out[k] = a.reshape(-1)[idx]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, a in out.items():
+        np.save(d / (f"{k}.npy" if world == 1 else f"{k}.rank{rank}.npy"), a)
+
+
+def timestep_index(i, i0, n):
+    """Step i of the run -> the index into the 50 DDIM timesteps (and the editors' step counter): i itself up to the last timestep, then round again
+    from i0, so that any number of warm-up + timed steps stays on steps i0 .. n - 1 (the editors' active range when i0 = 4)."""
+    return i if i < n else i0 + (i - i0) % (n - i0)
 
 
 def free_port() -> int:
@@ -299,19 +340,24 @@ def main():
             run(args.warmup)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(args.steps)
+        emb_out = run(args.steps)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        # the DDIM step around the inner loop costs a conditional forward before it and a batch-2 forward after it: a second run with twice the inner
-        # iterations separates the per-iteration time (slope) from that per-step overhead (intercept)
-        t1 = time.perf_counter()
-        run(2 * args.steps)
-        torch.cuda.synchronize()
-        dt2 = time.perf_counter() - t1
-        inner = (dt2 - dt) / args.steps
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {f"uncond_embeddings{i}": e for i, e in enumerate(emb_out)})
+        split = {}
+        if args.full:
+            # the DDIM step around the inner loop costs a conditional forward before it and a batch-2 forward after it: a second run with twice the inner
+            # iterations separates the per-iteration time (slope) from that per-step overhead (intercept)
+            t1 = time.perf_counter()
+            run(2 * args.steps)
+            torch.cuda.synchronize()
+            dt2 = time.perf_counter() - t1
+            inner = (dt2 - dt) / args.steps
+            split = {"inner_iteration_ms": round(inner * 1e3, 1), "ddim_step_overhead_ms": round((dt - inner * args.steps) * 1e3, 1)}
         print(json.dumps({"metric": "null-text inner iterations/sec (UNet forward on a tape + backward + Adam, batch 1; each timed call also runs the 2 plain forwards of its DDIM step)",
                           "value": round(args.steps / dt, 4), "unit": "iterations/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-                          "ms_per_step": round(dt / args.steps * 1e3, 1), "inner_iteration_ms": round(inner * 1e3, 1), "ddim_step_overhead_ms": round((dt - inner * args.steps) * 1e3, 1),
+                          "ms_per_step": round(dt / args.steps * 1e3, 1), **split,
                           "higher_is_better": True, "dtype": "f16 (fp32 gradient buffers, loss-scaled fp16 between layers)",
                           "data": "synthetic", "config": {"workload": f"{f} frames x {8*h}x{8*h}, single-branch UNet3D, sparse-causal attn1 (normal_infer=False as the reference hard-codes)",
                                                           "attention_backward": "fused flash-style me_attn_bwd (P rebuilt from the stashed log-sum-exp; key-centric dK / dV + query-centric dQ kernels)",
@@ -327,23 +373,27 @@ def main():
         for _ in range(args.warmup):
             vae.decode(z)
         torch.cuda.synchronize()
-        ops.PROFILE = []
+        ops.PROFILE = [] if args.full else None     # --full: an event pair around every launch of the timed steps (kernel_families)
         t0 = time.perf_counter()
         for _ in range(args.steps):
             img = vae.decode(z).sample
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         prof, ops.PROFILE = ops.PROFILE, None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"images": img})
         fam = {}
-        for rec in prof:
+        for rec in prof or []:
             d = fam.setdefault(rec[0], [0.0, 0.0])
             d[0] += rec[3].elapsed_time(rec[4]) * 1e-3
             d[1] += rec[1]
         assert torch.isfinite(img).all()
-        print(json.dumps({"metric": "vae-decode frames/sec (SD-1.5 AutoencoderKL decoder)", "value": round(args.frames * args.steps / dt, 3), "unit": "frames/s",
-                          "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
-                          "dtype": "f16", "data": "synthetic", "config": {"workload": f"{args.frames} latent frames {args.latent}x{args.latent} -> {8 * args.latent}x{8 * args.latent} images"},
-                          "kernel_families": {k: {"ms_per_step": round(v[0] / args.steps * 1e3, 2), "tflops": round(v[1] / v[0] / 1e12, 1) if v[0] else 0} for k, v in sorted(fam.items())}}))
+        out = {"metric": "vae-decode frames/sec (SD-1.5 AutoencoderKL decoder)", "value": round(args.frames * args.steps / dt, 3), "unit": "frames/s",
+               "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True,
+               "dtype": "f16", "data": "synthetic", "config": {"workload": f"{args.frames} latent frames {args.latent}x{args.latent} -> {8 * args.latent}x{8 * args.latent} images"}}
+        if args.full:
+            out["kernel_families"] = {k: {"ms_per_step": round(v[0] / args.steps * 1e3, 2), "tflops": round(v[1] / v[0] / 1e12, 1) if v[0] else 0} for k, v in sorted(fam.items())}
+        print(json.dumps(out))
         return
 
     usd = synth.synth_state_dict(synth.unet_schema())
@@ -427,8 +477,11 @@ def main():
     def run_step(i, lat):
         if args.inversion:   # one body of util.ddim_loop (reference util.py:118-123)
             return util.ddim_loop(pipe, pipe.scheduler, lat, 1, normal_infer=True, text_embeddings=cond[:1])[-1]
+        i = timestep_index(i, i0, len(ts))
         if args.editors == "inactive":
             sed.cur_step = ted.cur_step = 0      # the editors count steps themselves: hold them before start_step
+        else:
+            sed.cur_step = ted.cur_step = i      # what they count to by themselves, up to the last timestep; then round again with i
         if args.single_branch:
             emb1 = torch.cat([unc[i], cond[:1]])
             if use_graph and ops.PROFILE is None:
@@ -477,11 +530,13 @@ def main():
         dist.barrier()
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:   # the updated latents the last timed step returned (this rank's frames when the clip is sharded)
+        dump_outputs(args.dump_outputs, {"latents": lat}, rank, world)
     comm = None
     if dist_on:
         from motioneditor_amd import parallel
         comm = parallel.stats_summary(args.steps)
-        if not use_graph and args.steps + args.warmup + i0 + 2 <= len(ts):
+        if args.full and not use_graph and args.steps + args.warmup + i0 + 2 <= len(ts):
             # which exchanges hold the step's stream, and for how long: TWO more steps, untimed, with an event pair (CUDA) / clock pair (CPU tensors) around
             # every blocking exchange and every join of an asynchronous one (parallel.TIMING).  Kept out of the timed region (~400 event records per step);
             # every rank runs them (they contain the same collectives).  Not under --graph: events cannot be timed inside a captured step.
@@ -509,7 +564,7 @@ def main():
     plan_stats = None
     for st in pipe._plans.values():
         plan_stats = st["plan"].stats()
-    if not args.no_profile and not args.emulate:
+    if args.full and not args.no_profile and not args.emulate:
         ov = (pipe.overlap_controlnet, pipe.overlap_adapter)
         for st in pipe._plans.values():      # the recorded step's private pool goes back to the allocator before the eager pass needs the memory
             plan_stats = st["plan"].stats()
@@ -639,7 +694,7 @@ def main():
             out["kernel_families"] = {k: dict({"ms_per_step": round(v[0] / args.steps * 1e3, 2), "tflops": round(v[1] / v[0] / 1e12, 1) if v[0] else 0,
                                                "gbs": round(v[2] / v[0] / 1e9, 1) if v[0] else 0, "launches_per_step": v[3] // args.steps}, **roofs(v[1], v[2], v[0]))
                                       for k, v in sorted(fam.items())}
-        if world == 1 and not args.no_cpu_baseline and args.cpu_baseline != "off" and not args.emulate and not (args.single_branch or args.inversion):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.cpu_baseline != "off" and not args.emulate and not (args.single_branch or args.inversion):
             cdt, cores, cf, ch, cw = cpu_baseline(usd, csd)
             ctf, _ = step_tflop(cf, ch, cw)
             scale = tf_ref / ctf

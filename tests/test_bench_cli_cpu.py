@@ -12,7 +12,7 @@ ROOT = Path(__file__).resolve().parent.parent
 
 def test_bench_gpus_2_spawns_two_ranks_and_reports_them():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--emulate", "--frames", "8", "--latent", "8", "--steps", "1", "--warmup", "0"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--emulate", "--frames", "8", "--latent", "8", "--steps", "1", "--warmup", "0", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -108,3 +108,53 @@ def test_planned_or_eager_falls_back_only_while_nothing_was_replayed():
     import pytest as _pt
     with _pt.raises(RuntimeError):
         bench.planned_or_eager(p, st, 1, 0, None, None)
+
+
+def test_plain_run_times_the_steps_only_and_dumps_the_outputs(tmp_path):
+    """A plain run (no --full) reports the headline line without the extra passes; --dump-outputs writes the latents the last timed step returned, in
+    float32; the inputs are seeded, the same from run to run."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--emulate", "--frames", "8", "--latent", "8", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, env=env, cwd=str(ROOT))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["n_gpus"] == 1
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in d
+    for k in ("roofline", "kernels", "kernel_families", "cpu_baseline", "comm"):
+        assert k not in d
+    assert sorted(p.name for p in out.iterdir()) == ["latents.npy"]
+    a = np.load(out / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 4, 8, 8, 8) and np.isfinite(a).all()
+    sys.path.insert(0, str(ROOT))
+    import bench
+    x0 = bench.build_inputs(8, 8, 8)["latents"].numpy()
+    assert np.array_equal(x0, bench.build_inputs(8, 8, 8)["latents"].numpy()) and not np.array_equal(a, x0)   # seeded inputs; three steps moved them
+
+
+def test_dump_outputs_samples_large_outputs_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 16)
+    x = np.arange(40000, dtype=np.float64).reshape(200, 200)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, {"x": x, "y": np.ones(3, np.float16)})
+    sizes = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert sizes <= 1 << 16
+    a, b = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "b" / "x.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b) and 0 < a.size < x.size and np.all(np.diff(a) > 0)
+    bench.dump_outputs(tmp_path / "c", {"x": x[:10]}, rank=1, world=2)      # under the limit: the whole array, one file per rank
+    assert np.array_equal(np.load(tmp_path / "c" / "x.rank1.npy"), x[:10].astype(np.float32))
+
+
+def test_any_number_of_steps_stays_on_the_denoising_schedule():
+    """--steps / --warmup beyond the 50-step schedule: the step index goes round again over steps 4 .. 49 (editors active), unchanged up to 49."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    idx = [bench.timestep_index(i, 4, 50) for i in range(4, 200)]
+    assert idx[:46] == list(range(4, 50)) and idx[46:92] == list(range(4, 50)) and min(idx) == 4 and max(idx) == 49

@@ -9,7 +9,7 @@ for i in 1 2; do
 done
 for i in 1 2; do
   for lib in "" tools/_bin/libmotioned_gelu_scalar.so; do
-    ME_LIB=$lib python bench.py --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    ME_LIB=$lib python bench.py --full --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('${lib:-packed}', d['ms_per_step'], 'ms/step', {k:v['ms_per_step'] for k,v in d['kernel_families'].items()})"
   done

@@ -448,6 +448,26 @@ int me_cast_f16(void* dst, const float* src, int64_t n, void* stream);
 /* dst fp16 [rows, lddst] = src fp32 [rows, ldsrc] over columns [0, cols), zeros in [cols, pad_cols): a gradient view as the fp16 operand of the
  * input-gradient / weight-gradient MFMA kernels (pad_cols: the next multiple of 8 the transposed weights are padded to) */
 int me_cast_rows_f16(void* dst, int32_t lddst, const float* src, int32_t ldsrc, int64_t rows, int32_t cols, int32_t pad_cols, void* stream);
+/* Refresh of every weight derived from trained fp32 masters, in place, in one launch (the stage-1 UNet tuning step, util.UNetTuner).
+ * One descriptor per row range of a derived tensor; row r of entry d is global row d.row0 + r, entries in ascending row0 without gaps.
+ *   plain entry (gamma NULL):  dst[r, k] = f16(master[r, k])
+ *   fold entry  (gamma given): dst[r, k] = f16(master[r, k] * gamma[k])          (W' = W diag(gamma) of a LayerNorm-folded projection)
+ *                              colsum[r] = sum_k float(dst[r, k])                 (over the ROUNDED W', as weights.Packed.ln_fold)
+ *                              cvec[r]   = sum_k master[r, k] * beta[k] + (bias ? bias[r] : 0)
+ * K, ld_master, ld_dst: multiples of 4; master rows 16-byte, dst rows 8-byte aligned.  The table itself lives in DEVICE memory. */
+typedef struct me_refresh_desc {
+  const float* master;   /* fp32 [rows][ld_master] */
+  void* dst;             /* fp16 [rows][ld_dst] */
+  const float* gamma;    /* fp32 [K], NULL for a plain entry */
+  const float* beta;     /* fp32 [K] (fold entries) */
+  const float* bias;     /* fp32 [rows] or NULL (fold entries) */
+  float* colsum;         /* fp32 [rows] (fold entries) */
+  float* cvec;           /* fp32 [rows] (fold entries) */
+  int64_t row0;
+  int32_t rows, K, ld_master, ld_dst;
+} me_refresh_desc;
+
+int me_refresh_weights(const me_refresh_desc* table, int32_t n_entries, int64_t total_rows, void* stream);
 /* Loss seed of both optimisations: rec = ca * x + cb * (eps_u + guidance * (eps_c - eps_u)) (eps_c NULL: rec = ca * x + cb * eps_u; x NULL: no x term),
  * diff = rec - target (fp32 [nb, C, frames, npix], reference layout), d_eps[row, c] = coef * diff on channels-last rows (fp32, ld ldd).
  * prev_step + mse of p2p/null_text_optimization.py:26-36,150-151; the mse of train_adaptor.py:368 with ca = 0, cb = 1 */

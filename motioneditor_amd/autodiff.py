@@ -58,7 +58,7 @@ class Grads:
         self.buf: Dict[int, torch.Tensor] = {}
         self.fresh: set = set()                       # ids of allocations whose buffer exists but holds nothing yet (first-touch store pending)
         self.keep: List[torch.Tensor] = []
-        self.trainable = trainable or {}              # id(packed parameter tensor) -> its key in weights.Packed.cache
+        self.trainable = trainable or {}              # id(packed parameter tensor) -> its key in weights.Packed.cache, or [(row0, row1, key)] of its trained rows
         self.params: Dict[str, torch.Tensor] = param_buffers if param_buffers is not None else {}   # key -> fp32 gradient in the packed layout
 
     def wants(self, t: Optional[torch.Tensor]) -> bool:
@@ -72,6 +72,20 @@ class Grads:
         if g is None:
             g = self.params[k] = torch.zeros(t.shape, dtype=torch.float32, device=t.device)
         return g
+
+    def param_rows(self, t: torch.Tensor) -> Optional[List[Tuple[int, int, torch.Tensor]]]:
+        """A tensor trained on ROW RANGES (trainable[id(t)] = [(row0, row1, key)], weights.Packed.trainable_rows): [(row0, row1, fp32 gradient
+        buffer of rows row0:row1, packed layout)]; None for a tensor trained whole (trainable[id(t)] = key)."""
+        spec = self.trainable[id(t)]
+        if isinstance(spec, str):
+            return None
+        out = []
+        for r0, r1, k in spec:
+            g = self.params.get(k)
+            if g is None:
+                g = self.params[k] = torch.zeros((r1 - r0, *t.shape[1:]), dtype=torch.float32, device=t.device)
+            out.append((r0, r1, g))
+        return out
 
     def has(self, t: torch.Tensor) -> bool:
         return id(_base(t)) in self.buf
@@ -152,9 +166,19 @@ def _rule_gemm(B, x, w, out, kw):
         else:
             dpre = dy
         if G.wants(w):                                       # trainable weight: dW[n, tap, k] = sum_m dpre[m, n] * gather(x)[m, tap, k]
-            B.gemm_dw(dpre, x, dst=G.param(w), taps=taps, K=K, M=M, alpha=alpha, conv=kw.get("conv"), tconv=kw.get("tconv"))
+            rows = G.param_rows(w)
+            if rows is None:
+                B.gemm_dw(dpre, x, dst=G.param(w), taps=taps, K=K, M=M, alpha=alpha, conv=kw.get("conv"), tconv=kw.get("tconv"))
+            else:                                            # trained row ranges only (q of a fused q|k|v): frozen rows get no launch
+                for r0, r1, dst in rows:
+                    B.gemm_dw(dpre[:, r0:r1], x, dst=dst, taps=taps, K=K, M=M, alpha=alpha, conv=kw.get("conv"), tconv=kw.get("tconv"))
         if G.wants(kw.get("bias")):
-            B.colsum_grad(dpre[:M], dst=G.param(kw["bias"]))
+            rows = G.param_rows(kw["bias"])
+            if rows is None:
+                B.colsum_grad(dpre[:M], dst=G.param(kw["bias"]))
+            else:
+                for r0, r1, dst in rows:
+                    B.colsum_grad(dpre[:M, r0:r1], dst=dst)
         xv = x[:, :K]
         dst = G.view(xv, first_store=True)
         B.gemm_dx(dpre, w, dst=dst, M=M, alpha=alpha, conv=kw.get("conv"), tconv=kw.get("tconv"), store=G.take_fresh(xv))

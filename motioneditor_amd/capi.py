@@ -75,6 +75,14 @@ class GemmDwArgs(C.Structure):
     ]
 
 
+class RefreshDesc(C.Structure):
+    """me_refresh_desc: one row range of a weight derived from trained fp32 masters (me_refresh_weights)."""
+    _fields_ = [
+        ("master", _vp), ("dst", _vp), ("gamma", _vp), ("beta", _vp), ("bias", _vp), ("colsum", _vp), ("cvec", _vp),
+        ("row0", _i64), ("rows", _i32), ("K", _i32), ("ld_master", _i32), ("ld_dst", _i32),
+    ]
+
+
 class TAttnArgs(C.Structure):
     _fields_ = [
         ("Q", _vp), ("K", _vp), ("V", _vp), ("O", _vp),
@@ -162,6 +170,7 @@ SYMBOLS = {
     "me_adamw": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _f32, _vp]),
     "me_cast_f16": (C.c_int, [_vp, _vp, _i64, _vp]),
     "me_cast_rows_f16": (C.c_int, [_vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp]),
+    "me_refresh_weights": (C.c_int, [_vp, _i32, _i64, _vp]),
     "me_mse_seed": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _vp]),
     "me_nchw_to_rows": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "me_rows_to_nchw": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -330,6 +330,61 @@ __global__ __launch_bounds__(256) void cast_f16_kernel(f16* __restrict__ dst, co
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dst[i] = (f16)src[i];
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Derived-weight refresh (me_refresh_weights): one wave per row of the descriptor table's global row space, 4 columns per lane
+// and iteration (16-byte fp32 loads, 8-byte fp16 stores).  The wave finds its entry by a binary search over row0.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void refresh_weights_kernel(const me_refresh_desc* __restrict__ table, int n, long total_rows) {
+  // keeps every fp32 product apart from its fp16 rounding: otherwise the backend may fuse the two into v_fma_mix (ONE rounding of the exact
+  // product), which differs from Packed.ln_fold's two roundings in rare double-rounding cases -- even with contraction off
+#pragma clang fp exceptions(maytrap)
+  const int lane = threadIdx.x & 63;
+  const long gr = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (gr >= total_rows) return;
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {   // the last entry whose row0 <= gr
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[mid].row0 <= gr) lo = mid; else hi = mid - 1;
+  }
+  const me_refresh_desc d = table[lo];
+  const int r = (int)(gr - d.row0);
+  if (r < 0 || r >= d.rows) return;
+  const float* src = d.master + (long)r * d.ld_master;
+  f16* dst = reinterpret_cast<f16*>(d.dst) + (long)r * d.ld_dst;
+  if (!d.gamma) {
+    for (int k = lane * 4; k < d.K; k += 256) {
+      const f32x4 m = *reinterpret_cast<const f32x4*>(src + k);
+      *reinterpret_cast<f16x4*>(dst + k) = f16x4{(f16)m[0], (f16)m[1], (f16)m[2], (f16)m[3]};
+    }
+    return;
+  }
+  float cv = 0.f;
+  for (int k = lane * 4; k < d.K; k += 256) {
+    const f32x4 m = *reinterpret_cast<const f32x4*>(src + k);
+    const f32x4 g = *reinterpret_cast<const f32x4*>(d.gamma + k);
+    const f32x4 b = *reinterpret_cast<const f32x4*>(d.beta + k);
+    f16x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      o[j] = (f16)(m[j] * g[j]);   // one rounded fp32 product, then round-to-nearest-even: bitwise Packed.ln_fold
+      cv = fmaf(m[j], b[j], cv);
+    }
+    *reinterpret_cast<f16x4*>(dst + k) = o;
+  }
+  // colsum over the STORED W', read back by the lanes that wrote it
+  float cs = 0.f;
+  for (int k = lane * 4; k < d.K; k += 256) {
+    const f16x4 o = *reinterpret_cast<const f16x4*>(dst + k);
+    cs += ((float)o[0] + (float)o[1]) + ((float)o[2] + (float)o[3]);
+  }
+  cs = wave_sum(cs);
+  cv = wave_sum(cv);
+  if (lane == 0) {
+    d.colsum[r] = cs;
+    d.cvec[r] = d.bias ? cv + d.bias[r] : cv;
+  }
+}
+
 // dst fp16 [rows, lddst] <- src fp32 [rows, ldsrc], columns [0, cols) cast, [cols, pad_cols) zeroed (4 columns per thread)
 __global__ __launch_bounds__(256) void cast_rows_f16_kernel(f16* __restrict__ dst, int lddst, const float* __restrict__ src, int ldsrc, long rows, int cols, int pad_cols) {
   const int vpr = pad_cols / 4;
@@ -510,4 +565,12 @@ extern "C" int me_mse_seed(float* diff, float* d_eps, int32_t ldd, const void* e
   hipLaunchKernelGGL(mse_seed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), diff, d_eps, ldd,
                      reinterpret_cast<const f16*>(eps_u), ldu, reinterpret_cast<const f16*>(eps_c), ldc, x, target, nb, C, frames, npix, guidance, ca, cb, coef);
   ME_TRAIN_CHECK("me_mse_seed")
+}
+
+extern "C" int me_refresh_weights(const me_refresh_desc* table, int32_t n_entries, int64_t total_rows, void* stream) {
+  if (!table || n_entries <= 0 || total_rows <= 0 || ((uintptr_t)table & 7)) { me_set_error("me_refresh_weights: bad arguments"); return ME_EINVAL; }
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(refresh_weights_kernel, dim3((unsigned)((total_rows + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), table, (int)n_entries,
+                     (long)total_rows);
+  ME_TRAIN_CHECK("me_refresh_weights")
 }

@@ -464,6 +464,50 @@ def adapter_pack(P: Packed, prefix: str = "controlnet_adapter.") -> List[str]:
     return sorted(P.trainable_ids(prefix).values())
 
 
+def unet_tune_pack(P: Packed, names: Sequence[str]) -> List[str]:
+    """The packed tensors (cache keys) that hold the UNet parameters `names` in the single-branch forward as the autodiff tape records it
+    (LayerNorms not folded): what util.UNetTuner trains.  Built here, in the fusions unet_forward uses -- q|k|v of attn1 / attn_temp, every
+    block's attn2 k|v in the one text projection (text_kv_all), the GEGLU interleave of ff.net.0.proj.  (The motion adapter's parameters are
+    not reached by this forward -- it runs with ControlNet residuals only -- and the caller leaves them out.)  Every parameter whose packed form
+    is not a dense transformer-block projection -- 3x3 / temporal convolutions, norms (LayerNorm fold sources), the fused time_emb_proj,
+    proj_in / proj_out -- raises NotImplementedError naming it."""
+    blocks = {f"{b}.transformer_blocks.0": b for b in attention_block_names(True)}
+    text_kv = [f"{b}.transformer_blocks.0.attn2.{w}.weight" for b in attention_block_names(True) for w in ("to_k", "to_v")]
+    keys, bad = [], []
+    for n in names:
+        parts = n.split(".")
+        head = ".".join(parts[:5]) if parts[0] == "mid_block" else ".".join(parts[:6])
+        tail = n[len(head) + 1:]
+        if head not in blocks:
+            bad.append(n)
+            continue
+        if tail in ("attn1.to_q.weight", "attn1.to_k.weight", "attn1.to_v.weight", "attn_temp.to_q.weight", "attn_temp.to_k.weight", "attn_temp.to_v.weight"):
+            a = tail.split(".")[0]
+            P.fused([f"{head}.{a}.to_q.weight", f"{head}.{a}.to_k.weight", f"{head}.{a}.to_v.weight"])
+            keys.append("fused:" + "|".join(f"{head}.{a}.to_{x}.weight" for x in "qkv"))
+        elif tail == "attn2.to_q.weight" or tail.endswith(("to_out.0.weight", "ff.net.2.weight")) and tail.split(".")[0] in ("attn1", "attn2", "attn_temp", "ff"):
+            P.mat(n)
+            keys.append("mat:" + n)
+        elif tail.endswith(("to_out.0.bias", "ff.net.2.bias")) and tail.split(".")[0] in ("attn1", "attn2", "attn_temp", "ff"):
+            P.vec(n)
+            keys.append("vec:" + n)
+        elif tail in ("attn2.to_k.weight", "attn2.to_v.weight"):
+            P.fused(text_kv)
+            keys.append("fused:" + "|".join(text_kv))
+        elif tail == "ff.net.0.proj.weight":
+            P.geglu_mat(n)
+            keys.append("geglu:" + n)
+        elif tail == "ff.net.0.proj.bias":
+            P.geglu_vec(n)
+            keys.append("gegluv:" + n)
+        else:
+            bad.append(n)
+    if bad:
+        raise NotImplementedError(f"UNet tuning trains the dense transformer-block projections (attn1, attn2, attn_temp, ff) only; {len(bad)} selected "
+                                  f"parameter(s) are not supported: {bad[:8]}")
+    return sorted(set(keys))
+
+
 # ---------------------------------------------------------------------------------------------
 # UNet3D (unet_2d_condition.py:363-546)
 # ---------------------------------------------------------------------------------------------

@@ -871,3 +871,47 @@ def mse_seed(eps_u: torch.Tensor, target: torch.Tensor, *, eps_c: Optional[torch
     capi.check(capi.lib().me_mse_seed(diff.data_ptr(), d_eps.data_ptr(), d_eps.stride(0), eps_u.data_ptr(), eps_u.stride(0), _p(eps_c), 0 if eps_c is None else eps_c.stride(0),
                                       _p(x), target.data_ptr(), nb, Cc, f, h * w, float(guidance), float(ca), float(cb), float(coef), _stream()), "me_mse_seed")
     return diff, d_eps
+
+
+class RefreshTable:
+    """A device-resident me_refresh_desc table (refresh_table) and the tensors its pointers name, kept alive with it."""
+
+    def __init__(self, buf: torch.Tensor, n: int, total_rows: int, keep):
+        self.buf, self.n, self.total_rows, self.keep = buf, n, total_rows, keep
+
+
+def refresh_table(entries) -> RefreshTable:
+    """entries: (master fp32 [rows, ld] view, dst fp16 [rows, ld] view, gamma, beta, bias, colsum, cvec) -- the last five None for a plain entry
+    (dst = f16(master)); with gamma (fp32 [K]), beta (fp32 [K]), colsum / cvec (fp32 [rows] views) and an optional bias (fp32 [rows]) a LayerNorm-fold
+    entry (dst = f16(master * gamma), colsum = row sums of dst, cvec = master beta + bias).  Columns: the first K = master.shape[1] of each row.
+    Validated here, then copied to the device once: me_refresh_weights reads it on every launch."""
+    descs = (capi.RefreshDesc * len(entries))()
+    row0 = 0
+    keep = []
+    for i, (m, d, gamma, beta, bias, colsum, cvec) in enumerate(entries):
+        rows, K = m.shape
+        if m.dtype != torch.float32 or d.dtype != F16 or m.dim() != 2 or d.dim() != 2 or tuple(d.shape) != (rows, K) or m.stride(1) != 1 or d.stride(1) != 1:
+            raise ValueError("refresh_table: master fp32 and dst fp16 [rows, K] views of equal shape, unit column stride")
+        if K % 4 or m.stride(0) % 4 or d.stride(0) % 4 or (m.data_ptr() & 15) or (d.data_ptr() & 7) or not m.is_cuda or m.device != d.device:
+            raise ValueError("refresh_table: K and row strides multiples of 4, master 16-byte and dst 8-byte aligned, one device")
+        if (gamma is None) != (beta is None) or (gamma is None) != (colsum is None) or (gamma is None) != (cvec is None) or (gamma is None and bias is not None):
+            raise ValueError("refresh_table: a fold entry names gamma, beta, colsum and cvec; a plain entry none of them")
+        if gamma is not None:
+            for t, n in ((gamma, K), (beta, K), (colsum, rows), (cvec, rows), (bias, rows)):
+                if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or (t.data_ptr() & 15 and n == K) or t.device != m.device):
+                    raise ValueError("refresh_table: fold vectors fp32, contiguous, of K (gamma, beta) or rows (colsum, cvec, bias) elements, on the master's device")
+        e = descs[i]
+        e.master, e.dst, e.gamma, e.beta, e.bias, e.colsum, e.cvec = m.data_ptr(), d.data_ptr(), _p(gamma), _p(beta), _p(bias), _p(colsum), _p(cvec)
+        e.row0, e.rows, e.K, e.ld_master, e.ld_dst = row0, rows, K, m.stride(0), d.stride(0)
+        row0 += rows
+        keep.extend(t for t in (m, d, gamma, beta, bias, colsum, cvec) if t is not None)
+    if not entries:
+        raise ValueError("refresh_table: no entries")
+    host = torch.frombuffer(bytearray(C.string_at(C.addressof(descs), C.sizeof(descs))), dtype=torch.uint8)
+    dev = entries[0][0].device
+    return RefreshTable(host.to(dev), len(entries), row0, keep)
+
+
+def refresh_weights(table: RefreshTable) -> None:
+    """Every row of the table's entries refreshed from its fp32 master, in place, in ONE launch (me_refresh_weights)."""
+    capi.check(capi.lib().me_refresh_weights(table.buf.data_ptr(), table.n, table.total_rows, _stream()), "me_refresh_weights")

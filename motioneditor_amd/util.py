@@ -138,19 +138,20 @@ def null_optimization(pipeline, ddim_scheduler, latents, context: torch.Tensor, 
 # ---------------------------------------------------------------------------------------------------------------------
 # Adapter training step, the arithmetic of train_adaptor.py:364-368
 # ---------------------------------------------------------------------------------------------------------------------
-def _adapter_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, prefix, param_buffers=None,
-                      sync_amax=None):
-    """Forward on the tape, loss, backward.  -> (loss, loss scale, gradient store); the parameter gradients (packed layouts, times the loss
-    scale) are accumulated into `param_buffers[key]` when given.  sync_amax: callable(tensor [2]) that makes the seed magnitude -- and with it
-    the loss scale -- the same on every data-parallel rank (a MAX all-reduce), so that the gradient buckets can be summed."""
+def _unet_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, trainable, param_buffers=None,
+                   sync_amax=None):
+    """Forward on the tape, loss, backward.  -> (loss, loss scale, gradient store); the gradients of the packed tensors `trainable()` names after the
+    forward (autodiff.backward's `trainable`; packed layouts, times the loss scale) are accumulated into `param_buffers[key]` when given.  No residuals (None, None): the plain UNet forward.
+    sync_amax: callable(tensor [2]) that makes the seed magnitude -- and with it the loss scale -- the same on every data-parallel rank (a MAX
+    all-reduce), so that the gradient buckets can be summed."""
     from . import autodiff
     from .models import graph
     B_ = graph.ops
     P = unet.P
     dev = unet.device
     rows = lambda r: r if r.dim() == 2 else B_.nchw5_to_rows(r.to(dev))   # noqa: E731
-    down = [rows(r) for r in down_block_res_samples]
-    mid = rows(mid_block_res_sample)
+    down = None if down_block_res_samples is None else [rows(r) for r in down_block_res_samples]
+    mid = None if mid_block_res_sample is None else rows(mid_block_res_sample)
     ehs = graph.text_rows(encoder_hidden_states.to(dev), P.dtype).clone()
     t = float(timestep.item() if torch.is_tensor(timestep) else timestep)
     with autodiff.record(graph) as tape:
@@ -162,7 +163,7 @@ def _adapter_backward(unet, noisy_latents, timestep, encoder_hidden_states, down
         sync_amax(amax)
     st = torch.cat([B_.sumsq_absmax(diff), amax]).tolist()
     loss, ls = st[0] / tgt.numel(), _loss_scale(st[3])
-    G = autodiff.backward(tape, [(act.t, d_rows)], trainable=P.trainable_ids(prefix), seed_scale=ls, param_buffers=param_buffers)
+    G = autodiff.backward(tape, [(act.t, d_rows)], trainable=trainable(), seed_scale=ls, param_buffers=param_buffers)
     return loss, ls, G
 
 
@@ -174,7 +175,7 @@ def adapter_training_grads(unet, noisy_latents: torch.Tensor, timestep, encoder_
     rest).  Residuals in the reference layout [b, C, f, h', w'] (ControlNet outputs, no gradient).  The forward is the ordinary
     launch graph on an autodiff tape.  This is the inspection / export form; the training step itself (AdapterTrainer) keeps the gradients
     on the device in the packed layouts."""
-    loss, ls, G = _adapter_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, prefix)
+    loss, ls, G = _unet_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, lambda: unet.P.trainable_ids(prefix))
     grads = {}
     for key, g in G.params.items():
         for name, gn in unet.P.unpack_grad(key, g).items():    # host copy in the reference layout
@@ -239,8 +240,8 @@ class AdapterTrainer:
         sync = None
         if dist_on:
             sync = lambda a: dist.all_reduce(a, op=dist.ReduceOp.MAX, group=self.group)   # noqa: E731  (one loss scale for every rank's bucket)
-        loss, ls, G = _adapter_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, self.prefix,
-                                        param_buffers=self.param_buffers, sync_amax=sync)
+        loss, ls, G = _unet_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target,
+                                     lambda: self.unet.P.trainable_ids(self.prefix), param_buffers=self.param_buffers, sync_amax=sync)
         stray = [k for k in G.params if k not in self.param_buffers]
         if stray:
             raise RuntimeError(f"a gradient reached packed tensors the trainer does not own: {stray[:3]}")
@@ -272,3 +273,220 @@ class AdapterTrainer:
         for name, val in out.items():    # the model's own state follows the training: state_dict() / named_parameters() / .to(device) see the trained values
             P.state[P.prefix + name] = val.detach().cpu().clone()
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Stage-1 background tuning of the UNet, the arithmetic of train_bg.py:162-174,202-208,326-350
+# ---------------------------------------------------------------------------------------------------------------------
+class UNetTuner:
+    """One optimisation step of train_bg.py (stage 1) on the device: the parameters that train_bg.py's module / parameter filter selects
+    (default: attn1.to_q, attn2.to_q and attn_temp of every transformer block) are trained on the plain UNet forward (no ControlNet residuals,
+    sparse-causal attn1) against mse(model_pred, target), with clip_grad_norm_(max_grad_norm) and AdamW (the reference's defaults: lr 3e-5,
+    betas (0.9, 0.999), weight decay 1e-2, eps 1e-8).
+
+    The gradient bucket holds exactly the selected parameters the forward REACHES: the filter also matches the motion adapter's attn_temp,
+    which this forward never runs -- torch.optim.AdamW skips those (their .grad stays None), so they are left out here and stay bitwise
+    unchanged.  A reached parameter with an exactly zero gradient still takes AdamW's weight-decay step.  Parameters are trained on row
+    ranges of the packed tensors that hold them (q of a fused q|k|v; k|v stay frozen and get no weight-gradient launch).
+
+    Every weight derived from a trained parameter -- the fp16 packed tensors and the LayerNorm folds (W diag(gamma), colsum, W beta + b) of
+    the inference forward -- is rewritten IN PLACE after each update by one me_refresh_weights launch, so that recorded plans and captured
+    graphs replay with the tuned weights; a derived tensor first built after tuning started is built from the live fp32 masters
+    (weights.Packed.live).  No gradient, master or optimiser moment visits the host.  `save_checkpoint(dir)` writes what stage 2 and
+    inference read back (checkpoint.load_unet_state_dict(resume_from_checkpoint=dir))."""
+
+    def __init__(self, unet, trainable_modules=("attn1.to_q", "attn2.to_q", "attn_temp"), trainable_params=(), lr: float = 3e-5, betas=(0.9, 0.999),
+                 weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, group=None):
+        from .models import graph
+        from .weights import select_trainable
+        self.unet, self.group, self.max_grad_norm = unet, group, max_grad_norm
+        self.lr, self.betas, self.weight_decay, self.eps = lr, betas, weight_decay, eps
+        self.steps = 0
+        self.skipped_steps = 0
+        P = unet.P
+        P.make_private()
+        selected = select_trainable([k[len(P.prefix):] for k in P.state if k.startswith(P.prefix)], trainable_modules, trainable_params)
+        self.unreached = sorted(n for n in selected if n.startswith("controlnet_adapter."))   # the adapter runs with ControlNet residuals only
+        self.names = sorted(n for n in selected if not n.startswith("controlnet_adapter."))
+        if not self.names:
+            raise ValueError("UNetTuner: the filter selects no parameter of the UNet forward")
+        keys = graph.unet_tune_pack(P, self.names)
+        want = set(self.names)
+        slots, seen = [], set()
+        for key in keys:
+            for r0, r1, n in P.row_ranges(key):
+                if n in want:
+                    if n in seen:
+                        raise RuntimeError(f"UNetTuner: {n} lies in two packed tensors of the forward")
+                    seen.add(n)
+                    slots.append((key, r0, r1, n))
+        if seen != want:
+            raise RuntimeError(f"UNetTuner: no packed tensor holds {sorted(want - seen)[:3]}")
+        dev = unet.device
+        off, o = {}, 0
+        for key, r0, r1, n in slots:
+            numel = (r1 - r0) * (P.cache[key][0].numel() if P.cache[key].dim() > 1 else 1)
+            off[n] = (o, numel)
+            o += (numel + 3) // 4 * 4                 # every slot 16-byte aligned (the refresh kernel's vector loads)
+        self.master = torch.zeros(max(o, 4), dtype=torch.float32, device=dev)
+        self.m, self.v, self.grad = torch.zeros_like(self.master), torch.zeros_like(self.master), torch.zeros_like(self.master)
+        self.slots = slots
+        self.kind = {n: key.partition(":")[0] for key, _, _, n in slots}
+        self.masters, self.param_buffers = {}, {}
+        packed = {}
+        for key, r0, r1, n in slots:
+            if key not in packed:
+                packed[key] = P.packed_f32(key)            # exact fp32 values, not the fp16-rounded packing
+            shape = (r1 - r0, *P.cache[key].shape[1:])
+            o, numel = off[n]
+            self.masters[n] = self.master[o:o + numel].view(shape)
+            self.masters[n].copy_(packed[key][r0:r1].reshape(shape))
+            self.param_buffers[n] = self.grad[o:o + numel].view(shape)
+        del packed
+        if P.device.type == "cpu":
+            # a CPU store's fp32 packing of a Linear can be a VIEW of the caller's state array; the refresh rewrites packed tensors in place
+            for key, t in list(P.cache.items()):
+                kind, _, joined = key.partition(":")
+                if kind in ("mat", "vec", "fused", "fvec", "geglu", "gegluv") and not want.isdisjoint(joined.split("|")):
+                    P.cache[key] = t.clone()
+        self.trainable = P.trainable_rows(keys, self.names)
+        for n in self.names:                               # derived tensors built from now on read the live masters (a copy: never a view of one)
+            P.live[n] = (lambda n=n: self._reference_layout(n).detach().to("cpu", copy=True))
+        self._consts = {}
+        self._table, self._table_sig = None, None
+
+    # -- layouts ---------------------------------------------------------------------------------------------------------------------
+    def _reference_layout(self, n: str, t: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The master of `n` (or `t`, a tensor in the same packed layout) in the reference's own layout (Linear [N, K] or a vector)."""
+        t, kind = (self.masters[n] if t is None else t), self.kind[n]
+        if kind in ("geglu", "gegluv"):
+            from .weights import Packed
+            inv = torch.empty(t.shape[0], dtype=torch.long)
+            inv[Packed._geglu_perm(t.shape[0] // 2)] = torch.arange(t.shape[0])
+            t = t[inv.to(t.device)]
+        return t[:, 0, :] if t.dim() == 3 else t.reshape(-1)
+
+    def _const(self, key: str, make) -> torch.Tensor:
+        c = self._consts.get(key)
+        if c is None:
+            c = self._consts[key] = make().float().contiguous().to(self.unet.device)
+        return c
+
+    # -- the derived-weight refresh ----------------------------------------------------------------------------------------------------
+    def _refresh_entries(self):
+        """(entries for ops.refresh_table, 3-D tensors whose cached transposes go stale, signature of the cache entries they name)."""
+        P = self.unet.P
+        trained = set(self.names)
+        ents, stale, sig = [], [], []
+        for key, t in list(P.cache.items()):
+            kind, _, joined = key.partition(":")
+            ns = joined.split("|")
+            if kind not in ("mat", "vec", "fused", "fvec", "geglu", "gegluv", "lnw", "lnwg") or trained.isdisjoint(ns):
+                continue
+            if kind in ("lnw", "lnwg"):
+                wq, colsum, cvec = t
+                sig.append((key, wq.data_ptr(), colsum.data_ptr(), cvec.data_ptr()))
+                stale.append(wq)
+                norm_w, norm_b = ns[0], ns[1]
+                gamma = self._const("g:" + norm_w, lambda: P.raw(norm_w).reshape(-1))
+                beta = self._const("b:" + norm_b, lambda: P.raw(norm_b).reshape(-1))
+                bias = next((n for n in ns[2:] if n.endswith(".bias")), None)
+                bvec = None
+                if bias is not None:
+                    bvec = self.masters[bias].reshape(-1) if bias in trained else self._const(
+                        "lnbias:" + key, lambda: P.packed_f32(("gegluv:" if kind == "lnwg" else "vec:") + bias).reshape(-1))
+                K = wq.shape[2]
+                for r0, r1, n in P.row_ranges(key):
+                    if n not in trained and (bias is None or bias not in trained):
+                        continue
+                    src = self.masters[n].reshape(r1 - r0, K) if n in trained else self._const(
+                        "w:" + n, lambda: P.packed_f32(("geglu:" if kind == "lnwg" else "mat:") + n).reshape(r1 - r0, K))
+                    ents.append((src, wq[r0:r1].reshape(r1 - r0, K), gamma, beta, None if bvec is None else bvec[r0:r1], colsum[r0:r1], cvec[r0:r1]))
+                continue
+            sig.append((key, t.data_ptr()))
+            if t.dim() == 3:
+                stale.append(t)
+            for r0, r1, n in P.row_ranges(key):
+                if n in trained:
+                    if t.dim() == 1:
+                        ents.append((self.masters[n].reshape(1, -1), t[r0:r1].reshape(1, -1), None, None, None, None, None))
+                    else:
+                        ents.append((self.masters[n].reshape(r1 - r0, -1), t[r0:r1].reshape(r1 - r0, -1), None, None, None, None, None))
+        return ents, stale, tuple(sig)
+
+    def refresh(self) -> None:
+        """Rewrite every derived weight of the trained parameters from the fp32 masters, in place, in one launch."""
+        from .models import graph
+        B_ = graph.ops
+        ents, stale, sig = self._refresh_entries()
+        if sig != self._table_sig:
+            self._table = B_.refresh_table(ents)
+            self._table_sig = sig
+            self._stale = stale
+        B_.refresh_weights(self._table)
+        B_.invalidate_transposed(self._stale)
+
+    # -- the step ------------------------------------------------------------------------------------------------------------------------
+    def _world(self) -> int:
+        import torch.distributed as dist
+        return dist.get_world_size(self.group) if (dist.is_available() and dist.is_initialized()) else 1
+
+    def step(self, noisy_latents, timestep, encoder_hidden_states, target) -> float:
+        """train_bg.py:340-350 on one clip: model_pred = unet(noisy, t, ehs), loss = mse(model_pred, target), backward, clip, AdamW.  Returns the
+        loss (averaged over the ranks of a process group, as accelerator.gather(loss).mean())."""
+        import torch.distributed as dist
+        from .models import graph
+        B_ = graph.ops
+        world = self._world()
+        dist_on = dist.is_available() and dist.is_initialized()
+        self.grad.zero_()
+        sync = (lambda a: dist.all_reduce(a, op=dist.ReduceOp.MAX, group=self.group)) if dist_on else None
+        loss, ls, G = _unet_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, None, None, target, lambda: self.trainable,
+                                     param_buffers=self.param_buffers, sync_amax=sync)
+        stray = [k for k in G.params if k not in self.param_buffers]
+        if stray:
+            raise RuntimeError(f"a gradient reached packed tensors the tuner does not own: {stray[:3]}")
+        del G
+        if dist_on:
+            dist.all_reduce(self.grad, group=self.group)
+            lt = torch.tensor([loss], dtype=torch.float32, device=self.grad.device)
+            dist.all_reduce(lt, group=self.group)
+            loss = float(lt[0]) / world
+        gn = B_.sumsq_absmax(self.grad)
+        if not bool(torch.isfinite(gn.reshape(-1)[0])):
+            self.skipped_steps += 1          # fp16 overflow downstream of the seed: skip the update (accelerate's GradScaler does the same)
+            return loss
+        self.steps += 1
+        B_.adamw(self.master, self.m, self.v, self.grad, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, weight_decay=self.weight_decay,
+                 step=self.steps, gnorm_sq=gn, max_grad_norm=self.max_grad_norm, grad_scale=1.0 / (ls * world))
+        self.refresh()
+        return loss
+
+    def grads(self, noisy_latents, timestep, encoder_hidden_states, target):
+        """The inspection form of the step's backward (no update): (loss, {reference name: gradient, fp32 host tensor in the reference layout})
+        of every parameter in the bucket -- what loss.backward() leaves in .grad on the reference."""
+        self.grad.zero_()
+        loss, ls, G = _unet_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, None, None, target, lambda: self.trainable,
+                                     param_buffers=self.param_buffers)
+        del G
+        out = {n: self._reference_layout(n, self.param_buffers[n] / ls).cpu() for n in self.names}
+        self.grad.zero_()
+        return loss, out
+
+    # -- export --------------------------------------------------------------------------------------------------------------------------
+    def export_state_dict(self):
+        """{reference parameter name: fp32 host tensor in the reference layout} of the trained parameters."""
+        return {n: self._reference_layout(n).detach().cpu().clone() for n in self.names}
+
+    def save_checkpoint(self, directory) -> str:
+        """`directory`/model.safetensors: the full UNet state in the reference key schema, trained parameters at their current values (the model
+        weights of train_bg.py's checkpoint-N/; optimiser and RNG state are not written).  Returns the file's path."""
+        import os
+        from safetensors.torch import save_file
+        P = self.unet.P
+        out = {k[len(P.prefix):]: P.raw(k[len(P.prefix):]).contiguous().clone() for k in P.state if k.startswith(P.prefix)}
+        out.update(self.export_state_dict())
+        os.makedirs(directory, exist_ok=True)
+        path = os.path.join(str(directory), "model.safetensors")
+        save_file(out, path)
+        return path

@@ -15,7 +15,7 @@ Accepts numpy arrays or torch tensors (any float dtype) as values -- e.g. a real
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List, Mapping, Optional
+from typing import Callable, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -27,6 +27,18 @@ def _t(v) -> torch.Tensor:
     return v.detach().cpu()
 
 
+def select_trainable(names: Iterable[str], trainable_modules: Sequence[str] = (), trainable_params: Sequence[str] = ()) -> List[str]:
+    """The parameter selection of train_bg.py:162-174 over state-dict keys: `name` trains when one of the modules on its path (the `.`-prefixes
+    of the key) ends with one of `trainable_modules`, or when the key itself ends with one of `trainable_params`."""
+    mods, pars = tuple(trainable_modules), tuple(trainable_params)
+    out = []
+    for n in names:
+        parts = n.split(".")
+        if (mods and any(".".join(parts[:i]).endswith(mods) for i in range(1, len(parts)))) or (pars and n.endswith(pars)):
+            out.append(n)
+    return out
+
+
 class Packed:
     """name -> device fp16 tensor, packed lazily from the host state dict."""
 
@@ -36,6 +48,7 @@ class Packed:
         self.device = torch.device(device)
         self.prefix = prefix
         self.cache: Dict[str, torch.Tensor] = {}
+        self.live: Dict[str, Callable[[], torch.Tensor]] = {}   # reference name -> its current value while a trainer owns it (fp32 master, reference layout)
 
     def make_private(self) -> None:
         """Give this store its own (mutable) name -> tensor mapping before the first parameter is replaced: the caller's state dict -- often
@@ -48,6 +61,9 @@ class Packed:
         return (self.prefix + name) in self.state
 
     def raw(self, name: str) -> torch.Tensor:
+        src = self.live.get(name)
+        if src is not None:     # a trained parameter: a packed tensor first built during training comes from the live master, not the stale state
+            return src().float()
         return _t(self.state[self.prefix + name]).float()
 
     def _put(self, key: str, t: torch.Tensor) -> torch.Tensor:
@@ -175,6 +191,34 @@ class Packed:
             kind, _, names = key.partition(":")
             if isinstance(t, torch.Tensor) and kind in ("mat", "vec", "fused", "fvec", "geglu", "gegluv") and all(n.startswith(name_prefix) for n in names.split("|")):
                 out[id(t)] = key
+        return out
+
+    def row_ranges(self, key: str) -> List[Tuple[int, int, str]]:
+        """(row0, row1, reference name) of every parameter a packed tensor (or LayerNorm fold) `key` is built from, in row order.  A vector
+        (`vec:`, `fvec:`, `gegluv:`) counts its elements as rows.  GEGLU packings interleave value and gate rows of ONE parameter: one range."""
+        kind, _, names = key.partition(":")
+        ns = names.split("|")
+        rows_of = lambda n: int(self.state[self.prefix + n].shape[0])   # noqa: E731  (shapes from the state: never a live master's host copy)
+        if kind in ("lnw", "lnwg"):
+            ns = [n for n in ns[2:] if n.endswith(".weight")]   # norm.weight, norm.bias, projection(s)[, bias]
+            if kind == "lnwg":
+                return [(0, rows_of(ns[0]), ns[0])]
+        out, r = [], 0
+        for n in ns:
+            rows = rows_of(n)
+            out.append((r, r + rows, n))
+            r += rows
+        return out
+
+    def trainable_rows(self, keys: Iterable[str], names: Iterable[str]) -> Dict[int, List[Tuple[int, int, str]]]:
+        """id(packed tensor) -> [(row0, row1, reference name)] of the rows of each packed tensor `keys` that hold a parameter in `names`
+        (the trained row ranges of a partly-trained fused projection: q of q|k|v).  The autodiff tape computes weight gradients on those rows only."""
+        names = set(names)
+        out: Dict[int, List[Tuple[int, int, str]]] = {}
+        for key in keys:
+            rr = [r for r in self.row_ranges(key) if r[2] in names]
+            if rr:
+                out[id(self.cache[key])] = rr
         return out
 
     def update(self, name: str, value: torch.Tensor) -> None:

@@ -12,6 +12,9 @@ CLIP and the checkpoints (none exist offline):
     python examples/run_edit.py [--frames 8 --size 128 --steps 10 --inv-steps 10]      (defaults finish in seconds on one MI355X)
     python examples/run_edit.py --frames 24 --size 512 --steps 50 --inv-steps 50        (the reference's case-1 geometry)
 Without a text encoder the prompt embeddings enter as tensors (`text_embeddings`, `negative_text_embeddings`).
+    python examples/run_edit.py --prompt "a girl is dancing" --target-prompt "a boy is dancing" [--checkpoint SD15_DIR]
+encodes the prompts with the native CLIP classes instead (models.clip.CLIPTextModel, tokenizer.CLIPTokenizer): `text_encoder/` and `tokenizer/` of
+the checkpoint directory, or seeded synthetic weights and a byte-level vocabulary when none is given.
 """
 from __future__ import annotations
 
@@ -40,8 +43,9 @@ def harness_inputs(f: int, H: int, W: int, seed: int = 33) -> dict:
                 encode_noise=T(synth.synth_normal("harness.vae_noise", (f, 4, H // 8, W // 8), seed)))
 
 
-def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, output_type: str = "tensor", graphed: bool = False):
-    """inference.py:259-326 for one (source prompt, target prompt) pair.  Returns (sample_inv, sample_gen, ddim_inv_latent)."""
+def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, output_type: str = "tensor", graphed: bool = False, prompts=None):
+    """inference.py:259-326 for one (source prompt, target prompt) pair.  Returns (sample_inv, sample_gen, ddim_inv_latent).
+    prompts = [source, target]: the pipeline's own text encoder and tokenizer encode them (and the empty prompt) instead of the tensors in `x`."""
     from motioneditor_amd import util
     from motioneditor_amd.attn_control import (FullySelfAttentionControlMask, TemporalSelfAttentionControl,
                                                regiter_fully_attention_editor_diffusers, regiter_temporal_attention_editor_diffusers)
@@ -53,7 +57,7 @@ def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, out
     inv_sched = DDIMScheduler()
     inv_sched.set_timesteps(inv_steps)
     ddim_inv_latent = util.ddim_inversion(pipe, inv_sched, latents, inv_steps, prompt="", normal_infer=True,
-                                          text_embeddings=x["negative_text_embeddings"])[-1]             # (:288-293; prompt "" = the empty-prompt embedding)
+                                          text_embeddings=None if prompts else x["negative_text_embeddings"])[-1]   # (:288-293; prompt "" = the empty-prompt embedding)
     ddim_inv_latent = ddim_inv_latent.repeat(2, 1, 1, 1, 1)                                                # (:296)
     tgt = x["target_skeleton"]
     skeleton = torch.cat([torch.zeros_like(tgt), tgt, torch.zeros_like(tgt), tgt], dim=0)                  # (:300-302)
@@ -61,13 +65,22 @@ def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, out
     regiter_temporal_attention_editor_diffusers(pipe, ted)
     sed = FullySelfAttentionControlMask(start_step=4, start_layer=10, source_masks=x["source_masks"], target_masks=None, rectangle_source_masks=None)
     regiter_fully_attention_editor_diffusers(pipe, sed)
-    sample = pipe(["a source prompt", "a target prompt"], video_length=f, height=H, width=W, num_inference_steps=steps, guidance_scale=guidance,
-                  latents=ddim_inv_latent, uncond_embeddings=None, skeleton=skeleton, source_masks=None, target_masks=None,
-                  rectangle_source_masks=None, background_latents=None, output_type=output_type,
-                  text_embeddings=x["text_embeddings"], negative_text_embeddings=x["negative_text_embeddings"]).images
+    emb = {} if prompts else dict(text_embeddings=x["text_embeddings"], negative_text_embeddings=x["negative_text_embeddings"])
+    sample = pipe(list(prompts) if prompts else ["a source prompt", "a target prompt"], video_length=f, height=H, width=W, num_inference_steps=steps,
+                  guidance_scale=guidance, latents=ddim_inv_latent, uncond_embeddings=None, skeleton=skeleton, source_masks=None, target_masks=None,
+                  rectangle_source_masks=None, background_latents=None, output_type=output_type, **emb).images
     assert sample.shape[0] == 2
     sample_inv, sample_gen = sample.chunk(2)
     return sample_inv, sample_gen, ddim_inv_latent
+
+
+def text_models(checkpoint=None, device: str = "cuda"):
+    """(text_encoder, tokenizer): the native CLIP classes from an SD-1.5 checkpoint directory, or synthetic ones."""
+    from motioneditor_amd.models.clip import CLIPTextModel
+    from motioneditor_amd.tokenizer import CLIPTokenizer
+    if checkpoint:
+        return CLIPTextModel.from_pretrained(checkpoint, subfolder="text_encoder", device=device), CLIPTokenizer.from_pretrained(checkpoint, subfolder="tokenizer")
+    return CLIPTextModel.from_synthetic(device), CLIPTokenizer.from_synthetic()
 
 
 def build_pipeline(device: str = "cuda"):
@@ -88,13 +101,20 @@ def main():
     ap.add_argument("--executor", choices=["eager", "plan"], default="plan",
                     help="who issues the ~1100 launches of a denoising step: 'plan' = one me_denoise_step call per step (the launch list is recorded at the first step of "
                          "each editor gating, csrc/plan.hip), 'eager' = Python, launch by launch; the results are bitwise the same")
+    ap.add_argument("--prompt", default=None, help="source prompt: encode the prompts with the native CLIP text encoder instead of feeding synthetic embeddings")
+    ap.add_argument("--target-prompt", default=None, help="target prompt (default: the source prompt)")
+    ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
     a = ap.parse_args()
     pipe = build_pipeline()
     pipe.step_executor = a.executor
+    prompts = None
+    if a.prompt is not None:
+        pipe.text_encoder, pipe.tokenizer = text_models(a.checkpoint)
+        prompts = [a.prompt, a.target_prompt if a.target_prompt is not None else a.prompt]
     x = {k: v.cuda() for k, v in harness_inputs(a.frames, a.size, a.size).items()}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps)
+    inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps, prompts=prompts)
     torch.cuda.synchronize()
     print(f"{a.frames} frames {a.size}x{a.size}: encode + {a.inv_steps} inversion steps + {a.steps} denoising steps + decode in {time.perf_counter() - t0:.2f} s; "
           f"reconstruction {tuple(inv.shape)}, edit {tuple(gen.shape)}, range [{float(gen.min()):.3f}, {float(gen.max()):.3f}]")

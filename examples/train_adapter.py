@@ -7,7 +7,8 @@ tensors in place of the dataset, CLIP and the checkpoints (none exist offline):
     model_pred = unet(noisy, t, ehs, down_block_additional_residuals, mid_block_additional_residual).sample      (:364)
     loss = mse(model_pred, noise); backward; clip_grad_norm_(1.0); AdamW.step()  -- only controlnet_adapter.* trains (:365-384)
 
-    python examples/train_adapter.py [--frames 8 --size 128 --steps 2]
+    python examples/train_adapter.py [--frames 8 --size 128 --steps 2] [--prompt "a girl is dancing" [--checkpoint SD15_DIR]]
+--prompt: `ehs = text_encoder(prompt_ids)[0]` (train_adaptor.py:339) with the native CLIP classes instead of a synthetic embedding.
 Across GPUs: run under torchrun; util.AdapterTrainer averages the adapter gradients over the ranks in one all-reduced bucket.
 """
 from __future__ import annotations
@@ -38,6 +39,16 @@ def training_batch(f: int, H: int, W: int, seed: int = 7) -> dict:
                 noise=T(synth.synth_normal("train.noise", (1, 4, f, H // 8, W // 8), seed)))
 
 
+def encode_prompt(prompt: str, checkpoint=None, device: str = "cuda") -> torch.Tensor:
+    """train_adaptor.py:339 / train_bg.py:333: text_encoder(prompt_ids)[0] as a host tensor [1, 77, 768], through the native CLIP text encoder and tokenizer
+    (the checkpoint directory's, or synthetic ones)."""
+    sys.path.insert(0, str(ROOT / "examples"))
+    from run_edit import text_models
+    enc, tok = text_models(checkpoint, device)
+    ids = tok(prompt, max_length=tok.model_max_length, padding="max_length", truncation=True, return_tensors="pt").input_ids
+    return enc(ids)[0].cpu()
+
+
 def step(trainer, vae, controlnet, batch: dict, t: int) -> float:
     """train_adaptor.py:318-385 for one clip."""
     pv = batch["pixel_values"]
@@ -62,6 +73,8 @@ def main() -> None:
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--lr", type=float, default=3e-5)
+    ap.add_argument("--prompt", default=None, help="encode this prompt with the native CLIP text encoder instead of a synthetic embedding")
+    ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
     args = ap.parse_args()
     from motioneditor_amd import util
     from motioneditor_amd.models.controlnet import ControlNetModel
@@ -70,11 +83,14 @@ def main() -> None:
     dev = "cuda"
     vae, unet, cn = AutoencoderKL.from_synthetic(dev), UNet2DConditionModel.from_synthetic(dev), ControlNetModel.from_synthetic(dev)
     trainer = util.AdapterTrainer(unet, lr=args.lr)
+    ehs = encode_prompt(args.prompt, args.checkpoint, dev) if args.prompt is not None else None
     import time
     g = torch.Generator().manual_seed(0)
     for i in range(args.steps):
         t = int(torch.randint(0, 1000, (1,), generator=g))                                                         # (:335)
         batch = training_batch(args.frames, args.size, args.size, seed=7 + i)
+        if ehs is not None:
+            batch["ehs"] = ehs
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         loss = step(trainer, vae, cn, batch, t)

@@ -8,7 +8,8 @@ synthetic tensors in place of the dataset, CLIP and the SD-1.5 checkpoint (none 
 and the tuned UNet written as checkpoint-<steps>/model.safetensors -- what train_adaptor.py (one_stage_checkpoint) and inference.py
 (resume_from_checkpoint) read.
 
-    python examples/train_bg.py [--frames 8 --size 512 --steps 3 --lr 3e-5 --out runs/bg]
+    python examples/train_bg.py [--frames 8 --size 512 --steps 3 --lr 3e-5 --out runs/bg] [--prompt "a girl is dancing" [--checkpoint SD15_DIR]]
+--prompt: `encoder_hidden_states = text_encoder(prompt_ids)[0]` (:333) with the native CLIP classes instead of a synthetic embedding.
 Across GPUs: run under torchrun; util.UNetTuner averages the gradients over the ranks in one all-reduced bucket.
 """
 from __future__ import annotations
@@ -24,7 +25,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "examples"))
 
-from train_adapter import alphas_cumprod, training_batch  # noqa: E402
+from train_adapter import alphas_cumprod, encode_prompt, training_batch  # noqa: E402
 
 
 def step(tuner, vae, batch: dict, t: int) -> float:
@@ -47,6 +48,8 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--lr", type=float, default=3e-5)
     ap.add_argument("--out", default="runs/bg")
+    ap.add_argument("--prompt", default=None, help="encode this prompt with the native CLIP text encoder instead of a synthetic embedding")
+    ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
     args = ap.parse_args()
     from motioneditor_amd import util
     from motioneditor_amd.models.unet_2d_condition import UNet2DConditionModel
@@ -56,10 +59,13 @@ def main() -> None:
     tuner = util.UNetTuner(unet, lr=args.lr)
     print(f"training {len(tuner.names)} parameters ({tuner.master.numel() / 1e6:.1f} M values); {len(tuner.unreached)} selected parameters of the "
           "adapter are not reached by this forward and stay frozen")
+    ehs = encode_prompt(args.prompt, args.checkpoint, dev) if args.prompt is not None else None
     g = torch.Generator().manual_seed(0)
     for i in range(args.steps):
         t = int(torch.randint(0, 1000, (1,), generator=g))                                                         # (:334)
         batch = training_batch(args.frames, args.size, args.size, seed=7 + i)
+        if ehs is not None:
+            batch["ehs"] = ehs
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         loss = step(tuner, vae, batch, t)

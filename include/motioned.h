@@ -310,6 +310,20 @@ int me_copy_blocks(void* Y, int32_t ldy, const void* X, int32_t ldx, int32_t n0,
 int me_silu(void* Y, const void* X, int64_t n, void* stream);
 /* y = relu(x), n fp16 elements (adapter ResnetBlock.act, controlnet_adapter.py:452,504) */
 int me_relu(void* Y, const void* X, int64_t n, void* stream);
+/* ---- CLIP text encoder (csrc/clip.hip; transformers' CLIPTextModel, which pipeline_motion_editor.py:262-274 calls as
+ * text_encoder(input_ids)[0]).  LayerNorm and the dense projections of the encoder are me_layernorm / me_gemm. ---- */
+/* y = x * sigmoid(1.702 x) ("quick_gelu", the activation of the CLIP MLP), n fp16 elements, fp32 inside */
+int me_quick_gelu(void* Y, const void* X, int64_t n, void* stream);
+/* out[r, :] = fp16(tok[ids[r], :] + pos[r % seq, :]) for r < rows = n_seq * seq: token + position embedding.  tok fp16 [vocab][C], pos fp16 [seq][C],
+ * ids device int32 [rows], out fp16 [rows][C] contiguous; C a multiple of 8.  The caller checks the ids against the vocabulary (they come from the
+ * host); an id outside [0, vocab) that reaches the device reads nothing and leaves a zero row. */
+int me_embed_rows(void* out, const void* tok, const void* pos, const int32_t* ids, int64_t rows, int32_t seq, int32_t C, int32_t vocab, void* stream);
+/* Causal multi-head self-attention of short sequences: O[s, i, h] = softmax_{j <= i}(scale * Q[s,i,h] . K[s,j,h]) V[s,j,h], nk = nq <= 128, dh = 64.
+ * Q, K, V: fp16 column slices (row strides ldq / ldk / ldv in elements) of the fused projection output, rows ordered (sequence, position), head h at
+ * columns h * dh; O fp16 rows [n_seq * nq][>= heads * dh].  fp32 softmax with the row maximum subtracted; masked keys have weight exactly 0.
+ * No atomics: two runs are bitwise equal.  Any other dh, or nq > 128: ME_EINVAL. */
+int me_attn_causal(void* O, int32_t ldo, const void* Q, int32_t ldq, const void* K, int32_t ldk, const void* V, int32_t ldv, int32_t n_seq, int32_t heads,
+                   int32_t dh, int32_t nq, float scale, void* stream);
 /* sinusoidal timestep embedding, diffusers get_timestep_embedding(flip_sin_to_cos=True, shift=0):
  * out fp16 [rows, dim] all rows equal (unet_2d_condition.py:430-432) */
 int me_timestep_embed(void* out, int32_t rows, int32_t dim, float t, void* stream);

@@ -152,6 +152,9 @@ SYMBOLS = {
     "me_copy_blocks": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _i64, _i64, _i64, _vp]),
     "me_silu": (C.c_int, [_vp, _vp, _i64, _vp]),
     "me_relu": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "me_quick_gelu": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "me_embed_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "me_attn_causal": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
     "me_timestep_embed": (C.c_int, [_vp, _i32, _i32, _f32, _vp]),
     "me_cfg_ddim": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]),
     "me_timestep_embed_dev": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),

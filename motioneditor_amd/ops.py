@@ -486,6 +486,42 @@ def relu(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# -- CLIP text encoder (csrc/clip.hip; models/clip.py) --
+def quick_gelu(x: torch.Tensor) -> torch.Tensor:
+    """y = x * sigmoid(1.702 x) on a contiguous fp16 tensor (transformers' `quick_gelu`, the activation of the CLIP MLP)."""
+    if x.dtype != F16 or not x.is_contiguous():
+        raise ValueError("quick_gelu: contiguous fp16 input")
+    out = torch.empty_like(x)
+    capi.check(capi.lib().me_quick_gelu(out.data_ptr(), x.data_ptr(), x.numel(), _stream()), "me_quick_gelu")
+    return out
+
+
+def embed_rows(tok: torch.Tensor, pos: torch.Tensor, ids: torch.Tensor, seq: int) -> torch.Tensor:
+    """out[r] = tok[ids[r]] + pos[r % seq] as fp16 rows [ids.numel(), C]; tok [vocab, C], pos [>= seq, C] contiguous fp16, ids int32 on the device.
+    The ids are NOT checked here (that would be a device read-back): models/clip.py checks them on the host, where they come from."""
+    if tok.dtype != F16 or pos.dtype != F16 or tok.dim() != 2 or pos.dim() != 2 or not tok.is_contiguous() or not pos.is_contiguous() or tok.shape[1] != pos.shape[1]:
+        raise ValueError("embed_rows: tok [vocab, C] and pos [seq, C] must be contiguous fp16 tables of one width")
+    if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.device != tok.device or seq <= 0 or seq > pos.shape[0] or ids.numel() % seq:
+        raise ValueError("embed_rows: ids must be a contiguous int32 device tensor of n * seq entries, seq <= the position table")
+    rows, Cc = ids.numel(), tok.shape[1]
+    out = torch.empty((rows, Cc), dtype=F16, device=tok.device)
+    capi.check(capi.lib().me_embed_rows(out.data_ptr(), tok.data_ptr(), pos.data_ptr(), ids.data_ptr(), rows, seq, Cc, tok.shape[0], _stream()), "me_embed_rows")
+    return out
+
+
+def attention_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, heads: int, dh: int, n_seq: int, nq: int, scale: Optional[float] = None) -> torch.Tensor:
+    """Causal self-attention of n_seq sequences of nq <= 128 tokens at dh = 64 (me_attn_causal): q, k, v are [n_seq * nq, heads * dh] views (column slices
+    of the fused q | k | v projection), the result is a row tensor of the same shape."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v")):
+        _chk2d(t, "attention_causal." + n)
+        if t.shape[0] < n_seq * nq or t.shape[1] < heads * dh:
+            raise ValueError(f"attention_causal.{n}: expected at least [{n_seq * nq}, {heads * dh}], got {tuple(t.shape)}")
+    out = empty(n_seq * nq, heads * dh, q)
+    capi.check(capi.lib().me_attn_causal(out.data_ptr(), out.stride(0), q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                         n_seq, heads, dh, nq, dh ** -0.5 if scale is None else scale, _stream()), "me_attn_causal")
+    return out
+
+
 # Device-resident step scalars {t, guidance, ca, cb} (fp32 [4]) while a denoising step is captured into / replayed from a
 # hipGraph: the launches below then read them from memory instead of baking this step's values into the captured kernel
 # arguments.  Set by pipelines.MotionEditorPipeline.denoise_step_graphed; None = plain scalar arguments.

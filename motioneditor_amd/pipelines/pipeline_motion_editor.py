@@ -3,8 +3,10 @@
 rows, one batch-4 UNet3D forward with the content-aware motion adapter and both attention editors,
 classifier-free guidance and the DDIM update -- runs entirely on libmotioned HIP kernels.
 
-CLIP text encoding is out of scope: with no ``text_encoder`` the prompt embeddings are
-passed as ``text_embeddings=[2,77,768]`` (an extension keyword swallowed by the reference's ``**kwargs``).
+Prompts are strings when the pipeline holds a ``text_encoder`` and a ``tokenizer``: the native
+``models.clip.CLIPTextModel`` + ``tokenizer.CLIPTokenizer`` (libmotioned kernels, host-side BPE) or any pair with
+transformers' call surface.  With no ``text_encoder`` the prompt embeddings are passed as
+``text_embeddings=[2,77,768]`` (an extension keyword swallowed by the reference's ``**kwargs``).
 The VAE (``models/vae.py``) is optional: with no ``vae`` use ``output_type="latent"``.  DDIM inversion and
 null-text optimisation live in ``motioneditor_amd/util.py``.
 """
@@ -202,7 +204,8 @@ class MotionEditorPipeline:
             unc = negative_text_embeddings.to(device)
             return torch.cat([unc.expand(cond.shape[0], -1, -1) if unc.shape[0] == 1 else unc, cond])
         if self.text_encoder is None or self.tokenizer is None:
-            raise ValueError("no text_encoder/tokenizer: pass text_embeddings=[len(prompt),77,768] (CLIP encoding is out of scope)")
+            raise ValueError("no text_encoder/tokenizer: construct the pipeline with models.clip.CLIPTextModel and tokenizer.CLIPTokenizer, or pass "
+                             "text_embeddings=[len(prompt),77,768]")
 
         def enc(texts):
             ids = self.tokenizer(texts, padding="max_length", max_length=self.tokenizer.model_max_length, truncation=True, return_tensors="pt").input_ids

@@ -1,5 +1,5 @@
 """The reference harness sequence (inference.py:255-323) on motioneditor_amd, with synthetic tensors in place of the dataset,
-CLIP and the checkpoints (none exist offline):
+CLIP and the checkpoints (none exist offline) unless a clip folder is given (--video-dir):
 
     pixels [1, f, 3, H, W]  --vae.encode(...).latent_dist.sample() * 0.18215-->  latents [1, 4, f, h, w]      (:260-265)
     ddim_inversion(pipeline, scheduler, latents, num_inv_steps, prompt="", normal_infer=True)[-1]               (:288-293)
@@ -15,6 +15,10 @@ Without a text encoder the prompt embeddings enter as tensors (`text_embeddings`
     python examples/run_edit.py --prompt "a girl is dancing" --target-prompt "a boy is dancing" [--checkpoint SD15_DIR]
 encodes the prompts with the native CLIP classes instead (models.clip.CLIPTextModel, tokenizer.CLIPTokenizer): `text_encoder/` and `tokenizer/` of
 the checkpoint directory, or seeded synthetic weights and a byte-level vocabulary when none is given.
+    python examples/run_edit.py --video-dir data/case-1 --mask-dir man.mask [--condition openposefull --suffix .png] --out outputs/case-1
+reads the clip with data.dataset.VideoDataset (images/, man.mask/, source_condition/openposefull/, target_condition/openposefull/; --frames and --size are
+its n_sample_frames and width / height) and saves the edit and the reconstruction as sample/{target prompt}.gif and sample/{target prompt}-inv.gif under
+--out (inference.py:328-329).
 """
 from __future__ import annotations
 
@@ -41,6 +45,45 @@ def harness_inputs(f: int, H: int, W: int, seed: int = 33) -> dict:
                 text_embeddings=T(synth.synth_normal("harness.cond", (2, 77, 768), seed, 0.3)),        # CLIP(source prompt), CLIP(target prompt)
                 negative_text_embeddings=T(synth.synth_normal("harness.uncond", (1, 77, 768), seed, 0.3)),  # CLIP("")
                 encode_noise=T(synth.synth_normal("harness.vae_noise", (f, 4, H // 8, W // 8), seed)))
+
+
+def add_clip_arguments(ap: argparse.ArgumentParser) -> None:
+    """The flags that replace the synthetic clip by a folder on disk (shared by the three examples)."""
+    ap.add_argument("--video-dir", default=None, help="clip folder in the reference's data/case-N layout: images/, source_condition/<condition>/, target_condition/<condition>/, "
+                                                      "optionally <mask dir>/ and frame_list.txt (default: synthetic tensors)")
+    ap.add_argument("--mask-dir", default=None, help="folder of 0 / 255 foreground masks (.png) inside --video-dir, e.g. man.mask (default: all-ones masks)")
+    ap.add_argument("--condition", default="openposefull", help="condition folder name under source_condition/ and target_condition/")
+    ap.add_argument("--suffix", default=".png", help="file suffix of the frames in images/")
+
+
+def clip_batch(video_dir: str, f: int, H: int, W: int, *, prompt: str = "", mask_dir=None, condition: str = "openposefull", suffix: str = ".png",
+               device: str = "cuda") -> dict:
+    """One batch of VideoDataset as a DataLoader of batch size 1 delivers it (inference.py:249): every tensor with a leading 1."""
+    from motioneditor_amd.data.dataset import VideoDataset
+    ds = VideoDataset(video_dir, prompt, width=W, height=H, n_sample_frames=f, condition=[condition], video_suffix=suffix, source_mask_dir=mask_dir, device=device)
+    ex = ds[0]
+    lead = lambda t: t[None]   # noqa: E731
+    return dict(pixel_values=lead(ex["pixel_values"]), source_masks=lead(ex["source_masks"]), sample_indices=lead(ex["sample_indices"]),
+                source_conditions={k: lead(v) for k, v in ex["source_conditions"].items()}, target_conditions={k: lead(v) for k, v in ex["target_conditions"].items()},
+                prompt=[ex["prompt"]])
+
+
+def clip_inputs(a, device: str = "cuda") -> dict:
+    """harness_inputs with the clip of --video-dir in place of the synthetic pixels, target skeleton and masks (inference.py:254, 268, 270); the
+    embeddings and the VAE noise stay the seeded ones."""
+    x = {k: v.to(device) for k, v in harness_inputs(a.frames, a.size, a.size).items()}
+    b = clip_batch(a.video_dir, a.frames, a.size, a.size, prompt=a.prompt or "", mask_dir=a.mask_dir, condition=a.condition, suffix=a.suffix, device=device)
+    x.update(pixel_values=b["pixel_values"], target_skeleton=b["target_conditions"][a.condition], source_masks=b["source_masks"])
+    return x
+
+
+def save_samples(out_dir: str, target_prompt: str, sample_inv, sample_gen) -> list:
+    """inference.py:328-329."""
+    from motioneditor_amd import util
+    paths = [f"{out_dir}/sample/{target_prompt}.gif", f"{out_dir}/sample/{target_prompt}-inv.gif"]
+    util.save_videos_grid(sample_gen, paths[0])
+    util.save_videos_grid(sample_inv, paths[1])
+    return paths
 
 
 def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, output_type: str = "tensor", graphed: bool = False, prompts=None):
@@ -92,7 +135,7 @@ def build_pipeline(device: str = "cuda"):
                                 controlnet=ControlNetModel.from_synthetic(device))
 
 
-def main():
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--size", type=int, default=128)
@@ -104,20 +147,28 @@ def main():
     ap.add_argument("--prompt", default=None, help="source prompt: encode the prompts with the native CLIP text encoder instead of feeding synthetic embeddings")
     ap.add_argument("--target-prompt", default=None, help="target prompt (default: the source prompt)")
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
-    a = ap.parse_args()
+    add_clip_arguments(ap)
+    ap.add_argument("--out", default=None, help="directory that receives sample/{target prompt}.gif (the edit) and sample/{target prompt}-inv.gif (the reconstruction)")
+    return ap
+
+
+def main():
+    a = parser().parse_args()
     pipe = build_pipeline()
     pipe.step_executor = a.executor
     prompts = None
     if a.prompt is not None:
         pipe.text_encoder, pipe.tokenizer = text_models(a.checkpoint)
         prompts = [a.prompt, a.target_prompt if a.target_prompt is not None else a.prompt]
-    x = {k: v.cuda() for k, v in harness_inputs(a.frames, a.size, a.size).items()}
+    x = clip_inputs(a) if a.video_dir else {k: v.cuda() for k, v in harness_inputs(a.frames, a.size, a.size).items()}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps, prompts=prompts)
     torch.cuda.synchronize()
     print(f"{a.frames} frames {a.size}x{a.size}: encode + {a.inv_steps} inversion steps + {a.steps} denoising steps + decode in {time.perf_counter() - t0:.2f} s; "
           f"reconstruction {tuple(inv.shape)}, edit {tuple(gen.shape)}, range [{float(gen.min()):.3f}, {float(gen.max()):.3f}]")
+    if a.out:
+        print("saved", *save_samples(a.out, prompts[1] if prompts else "a target prompt", inv, gen))
 
 
 if __name__ == "__main__":

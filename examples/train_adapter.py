@@ -9,6 +9,8 @@ tensors in place of the dataset, CLIP and the checkpoints (none exist offline):
 
     python examples/train_adapter.py [--frames 8 --size 128 --steps 2] [--prompt "a girl is dancing" [--checkpoint SD15_DIR]]
 --prompt: `ehs = text_encoder(prompt_ids)[0]` (train_adaptor.py:339) with the native CLIP classes instead of a synthetic embedding.
+--video-dir DIR [--mask-dir man.mask --condition openposefull --suffix .png]: pixel_values and the source skeleton come from data.dataset.VideoDataset
+(train_adaptor.py:325, :348) instead of synthetic tensors; --frames and --size are its n_sample_frames and width / height.
 Across GPUs: run under torchrun; util.AdapterTrainer averages the adapter gradients over the ranks in one all-reduced bucket.
 """
 from __future__ import annotations
@@ -37,6 +39,15 @@ def training_batch(f: int, H: int, W: int, seed: int = 7) -> dict:
                 ehs=T(synth.synth_normal("train.ehs", (1, 77, 768), seed, 0.3)),
                 encode_noise=T(synth.synth_normal("train.vae_noise", (f, 4, H // 8, W // 8), seed)),
                 noise=T(synth.synth_normal("train.noise", (1, 4, f, H // 8, W // 8), seed)))
+
+
+def clip_training_batch(args, batch: dict) -> dict:
+    """`batch` with the clip of --video-dir in place of the synthetic pixels and skeleton (batch["source_conditions"][condition], train_adaptor.py:348)."""
+    sys.path.insert(0, str(ROOT / "examples"))
+    from run_edit import clip_batch
+    b = clip_batch(args.video_dir, args.frames, args.size, args.size, prompt=args.prompt or "", mask_dir=args.mask_dir, condition=args.condition, suffix=args.suffix)
+    batch.update(pixel_values=b["pixel_values"], skeleton=b["source_conditions"][args.condition])
+    return batch
 
 
 def encode_prompt(prompt: str, checkpoint=None, device: str = "cuda") -> torch.Tensor:
@@ -75,6 +86,9 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=3e-5)
     ap.add_argument("--prompt", default=None, help="encode this prompt with the native CLIP text encoder instead of a synthetic embedding")
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
+    sys.path.insert(0, str(ROOT / "examples"))
+    from run_edit import add_clip_arguments
+    add_clip_arguments(ap)
     args = ap.parse_args()
     from motioneditor_amd import util
     from motioneditor_amd.models.controlnet import ControlNetModel
@@ -91,6 +105,8 @@ def main() -> None:
         batch = training_batch(args.frames, args.size, args.size, seed=7 + i)
         if ehs is not None:
             batch["ehs"] = ehs
+        if args.video_dir:
+            batch = clip_training_batch(args, batch)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         loss = step(trainer, vae, cn, batch, t)

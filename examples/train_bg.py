@@ -10,6 +10,8 @@ and the tuned UNet written as checkpoint-<steps>/model.safetensors -- what train
 
     python examples/train_bg.py [--frames 8 --size 512 --steps 3 --lr 3e-5 --out runs/bg] [--prompt "a girl is dancing" [--checkpoint SD15_DIR]]
 --prompt: `encoder_hidden_states = text_encoder(prompt_ids)[0]` (:333) with the native CLIP classes instead of a synthetic embedding.
+--video-dir DIR [--mask-dir man.mask --condition openposefull --suffix .png]: pixel_values come from data.dataset.VideoDataset (train_bg.py:323) instead of
+synthetic tensors; --frames and --size are its n_sample_frames and width / height.
 Across GPUs: run under torchrun; util.UNetTuner averages the gradients over the ranks in one all-reduced bucket.
 """
 from __future__ import annotations
@@ -25,7 +27,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "examples"))
 
-from train_adapter import alphas_cumprod, encode_prompt, training_batch  # noqa: E402
+from run_edit import add_clip_arguments  # noqa: E402
+from train_adapter import alphas_cumprod, clip_training_batch, encode_prompt, training_batch  # noqa: E402
 
 
 def step(tuner, vae, batch: dict, t: int) -> float:
@@ -50,6 +53,7 @@ def main() -> None:
     ap.add_argument("--out", default="runs/bg")
     ap.add_argument("--prompt", default=None, help="encode this prompt with the native CLIP text encoder instead of a synthetic embedding")
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
+    add_clip_arguments(ap)
     args = ap.parse_args()
     from motioneditor_amd import util
     from motioneditor_amd.models.unet_2d_condition import UNet2DConditionModel
@@ -66,6 +70,8 @@ def main() -> None:
         batch = training_batch(args.frames, args.size, args.size, seed=7 + i)
         if ehs is not None:
             batch["ehs"] = ehs
+        if args.video_dir:
+            batch = clip_training_batch(args, batch)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         loss = step(tuner, vae, batch, t)

@@ -190,6 +190,13 @@ SYMBOLS = {
     "me_plan_destroy": (None, [_vp]),
 }
 
+# every symbol include/motioned_io.h declares (csrc/image.hip: clip I/O, outside the denoising-step ABI that ABI_VERSION numbers)
+RESIZE_BILINEAR, RESIZE_NEAREST = 0, 1
+IO_SYMBOLS = {
+    "me_image_resize": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
+    "me_video_grid_u8": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -210,7 +217,7 @@ def lib() -> C.CDLL:
         # and every launch would then fail with hipErrorNoDevice -- so make sure torch is loaded first.
         import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS}.items():
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         if L.me_abi_version() != ABI_VERSION:

@@ -522,6 +522,80 @@ def attention_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, heads
     return out
 
 
+# -- clip I/O (csrc/image.hip, include/motioned_io.h; data/dataset.py, util.save_videos_grid) --
+def _not_in_a_plan(what: str) -> None:
+    from . import plan
+    if plan.ACTIVE is not None:
+        raise RuntimeError(f"{what}: a denoising step is being recorded (plan.StepPlan.recording); clip I/O runs before and after the step, "
+                           "its launches do not belong in the step's plan")
+
+
+def grid_size(b: int, h: int, w: int, n_rows: int = 4) -> Tuple[int, int]:
+    """(Hg, Wg) of torchvision.utils.make_grid(x [b, c, h, w], nrow=n_rows): the image itself for b == 1, cells of (h + 2) x (w + 2) otherwise."""
+    if b == 1:
+        return h, w
+    xmaps = min(n_rows, b)
+    ymaps = (b + xmaps - 1) // xmaps
+    return (h + 2) * ymaps + 2, (w + 2) * xmaps + 2
+
+
+_RESIZE_MODES = {"bilinear": capi.RESIZE_BILINEAR, "nearest": capi.RESIZE_NEAREST}
+
+
+def image_resize(src: torch.Tensor, size: Tuple[int, int], mode: str = "bilinear", *, div: float = 1.0, add: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 images [n, H, W, C] (C = 1 or 3) or [n, H, W] on the device -> fp32 [n, C, oh, ow] = F.interpolate(x.float(), size=size, mode=mode) / div + add
+    (align_corners=False, no antialiasing; me_image_resize).  src and out may be views: unit stride along x (and C along the pixels of src), any image /
+    channel / row strides that keep rows, channels and images apart."""
+    _not_in_a_plan("image_resize")
+    if mode not in _RESIZE_MODES:
+        raise ValueError(f"image_resize: mode must be one of {sorted(_RESIZE_MODES)}, got {mode!r}")
+    if src.dtype != torch.uint8 or src.dim() not in (3, 4) or not src.is_cuda:
+        raise ValueError(f"image_resize: expected CUDA uint8 images [n, H, W, C] or [n, H, W], got {src.dtype} {tuple(src.shape)} on {src.device}")
+    n, H, W = src.shape[:3]
+    Cc = src.shape[3] if src.dim() == 4 else 1
+    oh, ow = int(size[0]), int(size[1])
+    if Cc not in (1, 3) or min(n, H, W) <= 0 or oh <= 0 or ow <= 0:
+        raise ValueError(f"image_resize: C must be 1 or 3 and every size positive, got src {tuple(src.shape)} -> {(oh, ow)}")
+    if (W > 1 and src.stride(2) != Cc) or (src.dim() == 4 and Cc > 1 and src.stride(3) != 1):
+        raise ValueError(f"image_resize: src must be interleaved along x (pixel stride C, channel stride 1), got strides {src.stride()}")
+    s_row = src.stride(1) if H > 1 else W * Cc
+    s_img = src.stride(0) if n > 1 else H * s_row
+    if out is None:
+        out = torch.empty((n, Cc, oh, ow), dtype=torch.float32, device=src.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (n, Cc, oh, ow) or out.device != src.device or (ow > 1 and out.stride(3) != 1):
+        raise ValueError(f"image_resize: out must be fp32 {(n, Cc, oh, ow)} on {src.device} with unit stride along x, got {out.dtype} {tuple(out.shape)} {out.stride()}")
+    o_row = out.stride(2) if oh > 1 else ow
+    o_ch = out.stride(1) if Cc > 1 else oh * o_row
+    o_img = out.stride(0) if n > 1 else Cc * o_ch
+    capi.check(capi.lib().me_image_resize(out.data_ptr(), o_img, o_ch, o_row, src.data_ptr(), s_img, s_row, n, H, W, Cc, oh, ow, _RESIZE_MODES[mode],
+                                          float(div), float(add), _stream()), "me_image_resize")
+    return out
+
+
+def video_grid_u8(videos: torch.Tensor, n_rows: int = 4, rescale: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 video [b, c, f, h, w] (c = 1 or 3, unit stride along x) on the device -> uint8 frames [f, Hg, Wg, 3]: per frame make_grid(x, nrow=n_rows),
+    (x + 1) / 2 when `rescale`, (x * 255) truncated to uint8 and clamped to [0, 255] (me_video_grid_u8; grid_size gives Hg, Wg)."""
+    _not_in_a_plan("video_grid_u8")
+    if videos.dtype != torch.float32 or videos.dim() != 5 or not videos.is_cuda:
+        raise ValueError(f"video_grid_u8: expected a CUDA fp32 video [b, c, f, h, w], got {videos.dtype} {tuple(videos.shape)} on {videos.device}")
+    b, c, f, h, w = videos.shape
+    if c not in (1, 3) or min(b, f, h, w) <= 0 or int(n_rows) <= 0:
+        raise ValueError(f"video_grid_u8: c must be 1 or 3, every size and n_rows positive, got {tuple(videos.shape)}, n_rows {n_rows}")
+    if (w > 1 and videos.stride(4) != 1) or min(videos.stride()) < 0:
+        raise ValueError(f"video_grid_u8: the video must have unit stride along x, got strides {videos.stride()}")
+    Hg, Wg = grid_size(b, h, w, int(n_rows))
+    if out is None:
+        out = torch.empty((f, Hg, Wg, 3), dtype=torch.uint8, device=videos.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (f, Hg, Wg, 3) or out.device != videos.device or out.stride(3) != 1 or out.stride(2) != 3:
+        raise ValueError(f"video_grid_u8: out must be uint8 {(f, Hg, Wg, 3)} on {videos.device}, interleaved along x, got {out.dtype} {tuple(out.shape)} {out.stride()}")
+    o_row = out.stride(1) if Hg > 1 else 3 * Wg
+    o_frame = out.stride(0) if f > 1 else Hg * o_row
+    s_row = videos.stride(3) if h > 1 else w
+    capi.check(capi.lib().me_video_grid_u8(out.data_ptr(), o_frame, o_row, videos.data_ptr(), videos.stride(0), videos.stride(1), videos.stride(2), s_row,
+                                           b, c, f, h, w, int(n_rows), 1 if rescale else 0, _stream()), "me_video_grid_u8")
+    return out
+
+
 # Device-resident step scalars {t, guidance, ca, cb} (fp32 [4]) while a denoising step is captured into / replayed from a
 # hipGraph: the launches below then read them from memory instead of baking this step's values into the captured kernel
 # arguments.  Set by pipelines.MotionEditorPipeline.denoise_step_graphed; None = plain scalar arguments.

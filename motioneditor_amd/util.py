@@ -490,3 +490,55 @@ class UNetTuner:
         path = os.path.join(str(directory), "model.safetensors")
         save_file(out, path)
         return path
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Video writers (reference `motion_editor/util.py:15-54`): same names and signatures.  The float -> uint8 grid is one device kernel
+# (ops.video_grid_u8, csrc/image.hip) and one device -> host copy of uint8 frames; PIL writes the files.
+# ---------------------------------------------------------------------------------------------------------------------
+UPLOAD_DEVICE = "cuda"   # where a CPU tensor handed to the writers is uploaded to (the no-GPU tests point it at "cpu", beside the emulated ops)
+GIF_FPS = 8   # util.py:46 `imageio.mimsave(path, outputs, fps=8)`: the GIF runs at 8 frames per second whatever `fps` says
+
+
+def videos_to_grid_frames(videos: torch.Tensor, rescale: bool = False, n_rows: int = 4) -> torch.Tensor:
+    """videos [b, c, t, h, w] (c = 1 or 3; a CPU tensor is uploaded first) -> uint8 host frames [t, Hg, Wg, 3]: per frame
+    torchvision.utils.make_grid(x, nrow=n_rows), `(x + 1.0) / 2.0` when `rescale`, `(x * 255)` as uint8 (util.py:35-43).  One launch, one copy."""
+    if not torch.is_tensor(videos) or videos.dim() != 5:
+        raise ValueError("videos_to_grid_frames: expected a tensor [b, c, t, h, w]")
+    v = videos.detach()
+    if not v.is_cuda:
+        v = v.to(UPLOAD_DEVICE)
+    if v.dtype != torch.float32:
+        v = v.float()
+    return ops.video_grid_u8(v, n_rows=n_rows, rescale=bool(rescale)).cpu()
+
+
+def save_videos_grid(videos: torch.Tensor, path: str, rescale=False, n_rows=4, fps=1):
+    """util.py:34-54.  Writes the GIF (PIL: save_all, loop=0, 1000 / 8 = 125 ms per frame -- the reference hard-codes fps=8 for the GIF and uses `fps`
+    only for the .mp4 twin it writes through imageio + ffmpeg).  The .mp4 is not written here (neither library exists on this platform), and a
+    path that ends in .mp4 is refused."""
+    import os
+    from PIL import Image
+    if str(path).lower().endswith(".mp4"):
+        raise ValueError(f"save_videos_grid: {path}: .mp4 needs imageio + ffmpeg, which this package does not use; give a .gif path "
+                         "(the reference's .mp4 twin of the GIF is not written)")
+    frames = videos_to_grid_frames(videos, rescale=rescale, n_rows=n_rows).numpy()
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    ims = [Image.fromarray(f) for f in frames]
+    ims[0].save(path, format="GIF", save_all=True, append_images=ims[1:], loop=0, duration=1000 // GIF_FPS)
+
+
+def save_videos_as_images(videos: torch.Tensor, path: str, rescale=False, n_rows=4, fps=1):
+    """util.py:15-31: `path`/vis_images/batch_{b}/frame_{t}.png, one lossless PNG per batch entry and frame (n_rows and fps are unused, as there)."""
+    import os
+    from PIL import Image
+    if not torch.is_tensor(videos) or videos.dim() != 5:
+        raise ValueError("save_videos_as_images: expected a tensor [b, c, t, h, w]")
+    os.makedirs(os.path.join(path, "vis_images"), exist_ok=True)
+    for batch_idx in range(videos.shape[0]):
+        frames = videos_to_grid_frames(videos[batch_idx:batch_idx + 1], rescale=rescale).numpy()     # b = 1: the frame is the image itself
+        save_dir = os.path.join(path, "vis_images", f"batch_{batch_idx}")
+        os.makedirs(save_dir, exist_ok=True)
+        for frame_idx, image in enumerate(frames):
+            Image.fromarray(image).save(os.path.join(save_dir, f"frame_{frame_idx}.png"))

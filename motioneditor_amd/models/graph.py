@@ -674,6 +674,11 @@ def unet_forward(P: Packed, sample: torch.Tensor, t: float, ehs: torch.Tensor, *
     n = "mid_block.resnets.1"
     x = resnet_block(P, n, x, temb, toff[n], per_frame_stats=False, shard=shard)
     if mid_res is not None:
+        if side is not None and res_ready is not None:
+            # ControlNet wrote mid_res on the side stream and main has not waited on anything of that stream yet (its first wait below, adapter_done,
+            # comes after this add): order the residual's producer before its reader.  On `res_ready`, not on adapter_done moved up: the adapter
+            # stays overlapped with the mid block.  (tests/test_streamcheck_gpu.py finds the missing edge in the recorded launch list.)
+            plan.wait_event(torch.cuda.current_stream(), res_ready)
         if two_branch:
             nr = x.f * x.N
             for k, eb in enumerate(edit_rows):

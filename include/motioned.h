@@ -361,9 +361,11 @@ int me_softmax_rows(void* Y, int32_t ldy, const void* X, int32_t ldx, int64_t ro
  * The input gradient of me_gemm needs no entry of its own: it is me_gemm on transposed, tap-reversed weights.
  */
 /* GEGLU (attention_2d.py FeedForward/GEGLU): pre = biased pre-activation [M, N] fp16 in the packed (16 value | 16 gate) column
- * order, dy fp32 [M, N/2] -> dpre fp16 [M, N] */
+ * order, dy fp32 [M, N/2] -> dpre fp16 [M, N].  N % 32 == 0; ldd, ldp >= N and lddy >= N / 2 (rows must not overlap); pointers aligned
+ * to their element type.  A product beyond fp16's range becomes +-inf of its sign (round to nearest), finite neighbours are unaffected. */
 int me_geglu_bwd(void* dpre, int32_t ldd, const void* pre, int32_t ldp, const void* dy, int32_t lddy, int64_t M, int32_t N, void* stream);
-/* nn.LayerNorm: dx fp32 [rows, C] from x fp16, gamma fp16, dy fp32 */
+/* nn.LayerNorm: dx fp32 [rows, C] from x fp16, gamma fp16, dy fp32.  Element-wise accesses: no vector alignment is required, only naturally
+ * aligned pointers and row strides ldx, lddx, lddy >= C */
 int me_layernorm_bwd(void* dx, int32_t lddx, const void* x, int32_t ldx, const void* gamma, const void* dy, int32_t lddy, int64_t rows, int32_t C, float eps,
                      void* stream);
 /* GroupNorm (+ SiLU when silu != 0; statistics over rows_per_group rows x C/groups channels, as me_groupnorm): dx fp32.  Row-parallel passes
@@ -373,7 +375,9 @@ int me_groupnorm_bwd(void* dx, int32_t lddx, const void* x, int32_t ldx, const v
 int64_t me_groupnorm_bwd_scratch_bytes(int32_t rows, int32_t rows_per_group, int32_t groups);
 
 /* Temporal causal attention (me_tattn, plain row order, identity kv_map): dq, dk, dv fp32 [batch*frames*npix, ld] from q, k, v fp16
- * and dout fp32; frames <= 64 */
+ * and dout fp32; frames <= 64, dh in {40, 80, 160}, every row stride >= heads * dh; frames * dh must fit the LDS tile (frames = 64 with
+ * dh = 160 does not: ME_EINVAL).  frames <= 32 with 16-byte aligned rows and heads a multiple of 8 / 4 / 2 (dh 40 / 80 / 160) takes the
+ * lane-parallel kernel (me_last_kernel: "tattn_bwd2_kernel<DH,HB>"), everything else the first version ("tattn_bwd_kernel") */
 int me_tattn_bwd(void* dq, int32_t lddq, void* dk, int32_t lddk, void* dv, int32_t lddv, const void* q, int32_t ldq, const void* k, int32_t ldk, const void* v, int32_t ldv,
                  const void* dout, int32_t lddo, int32_t batch, int32_t frames, int32_t npix, int32_t heads, int32_t dh, float scale, void* stream);
 
@@ -413,6 +417,8 @@ typedef struct me_attn_bwd_args {
   float scale;
 } me_attn_bwd_args;
 
+/* Every row stride must cover heads * dh columns (narrower rows would overlap and the accumulation into dQ / dK / dV race), be a multiple of 8
+ * (fp16 tensors) / 4 (fp32 gradients), and the tensor pointers 16-byte aligned: ME_EINVAL otherwise. */
 int me_attn_bwd(const me_attn_bwd_args* a, void* stream);
 
 /* ---- parameter gradients, gradient bookkeeping, optimiser ------------------------------------- *
@@ -434,7 +440,7 @@ typedef struct me_gemm_dw_args {
 
 int me_gemm_dw(const me_gemm_dw_args* a, void* stream);
 int64_t me_gemm_dw_work_bytes(int32_t M, int32_t N, int32_t K);
-/* out[n] += alpha * sum_m dY[m, n]  (bias gradients); work: me_colsum_work_bytes(N) bytes */
+/* out[n] += alpha * sum_m dY[m, n]  (bias gradients); work: me_colsum_work_bytes(N) bytes.  lddy >= N; pointers aligned to their element type. */
 int me_colsum(float* out, const void* dY, int32_t lddy, int32_t dy_is_f16, int64_t M, int32_t N, float alpha, float* work, void* stream);
 int64_t me_colsum_work_bytes(int32_t N);
 /* nn.LayerNorm parameter gradients: dgamma[c] += alpha * sum_m dy[m, c] xhat[m, c], dbeta[c] += alpha * sum_m dy[m, c] (either may be NULL);
@@ -449,12 +455,21 @@ int64_t me_layernorm_bwd_params_work_bytes(int64_t rows, int32_t C);
  * buffer that was allocated but never zeroed (saves the fill and the read) */
 int me_grad_acc(void* dst, int32_t lddst, const void* src, int32_t ldsrc, int32_t src_is_f16, int64_t rows, int32_t cols, float alpha, int32_t pool_h, int32_t pool_w,
                 void* stream);
-/* out = {sum x^2, max |x|} of an fp32 vector (gradient-norm clipping, loss, loss-scale selection); work: me_sumsq_work_bytes() bytes */
+/* out = {sum x^2, max |x|} of an fp32 vector (gradient-norm clipping, loss, loss-scale selection); work: me_sumsq_work_bytes() bytes.
+ * Non-finite input: both outputs are non-finite whenever x holds a non-finite element -- a NaN anywhere makes out[0] and out[1] NaN, an
+ * +-inf (and no NaN) makes both +inf.  max |x| PROPAGATES NaN (it is not fmaxf, which drops one), so isfinite(out[1]) is the test "every
+ * element was finite" that the loss-scale selection and the trainers' skipped-step rule rely on.  Finite input: out[1] is exact, and the
+ * result is bitwise reproducible (fixed-order reduction).  n >= 1. */
 int me_sumsq_absmax(float* out, const float* x, int64_t n, float* work, void* stream);
 int64_t me_sumsq_work_bytes(void);
 /* One AdamW step on fp32 master parameters (torch.optim.AdamW; weight_decay 0 = torch.optim.Adam).  bias_c1 = 1 - beta1^t, bias_c2 = 1 - beta2^t.
  * The gradient used is g * grad_scale * clip, clip = min(1, max_grad_norm / (sqrt(gnorm_sq[0]) * grad_scale + 1e-6)) when gnorm_sq (a DEVICE
- * scalar, me_sumsq_absmax's out[0] over the whole gradient bucket) is given -- torch.nn.utils.clip_grad_norm_ without a host round trip */
+ * scalar, me_sumsq_absmax's out[0] over the whole gradient bucket) is given -- torch.nn.utils.clip_grad_norm_ without a host round trip.
+ * Non-finite norm: when gnorm_sq is given and gnorm_sq[0] is +inf or NaN (an fp16 overflow upstream of the bucket), the call is a NO-OP -- p, m
+ * and v stay bitwise unchanged and ME_OK is returned; the caller counts the skipped step.  Without gnorm_sq nothing is screened: a non-finite
+ * g[i] reaches p[i], m[i] and v[i].  bias_c1, bias_c2 > 0 and n >= 1 are required (ME_EINVAL otherwise).
+ * The hyper-parameters are the fp32 values passed: 1 - beta1 and 1 - beta2 are formed (exactly) from the fp32 beta1 and beta2, so with
+ * beta2 = 0.999f the weight of g^2 in v is 1.2e-5 (relative) away from the 0.001 of a double-precision 1 - 0.999. */
 int me_adamw(float* p, float* m, float* v, const float* g, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, float bias_c1, float bias_c2,
              const float* gnorm_sq, float max_grad_norm, float grad_scale, void* stream);
 /* dst fp16 [n] = src fp32 [n]: refresh of the packed fp16 weights from their fp32 masters */

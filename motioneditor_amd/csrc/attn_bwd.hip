@@ -424,7 +424,9 @@ int launch_bwd(const me_attn_bwd_args* a, hipStream_t st) {
   hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH, NKT>), dim3((unsigned)((long)a->n_kv_items * a->heads * nkb)), dim3(256), 0, st, *a);
   const int nqb = (a->nq + 63) / 64;
   hipLaunchKernelGGL((attn_bwd_dq_kernel<DH, (DH > 80 ? 32 : 64)>), dim3((unsigned)((long)a->n_items * a->heads * nqb)), dim3(256), 0, st, *a);
-  me_set_kernel("attn_bwd_dkv_kernel+attn_bwd_dq_kernel");
+  char nm[64];
+  snprintf(nm, sizeof(nm), "attn_bwd_dkv_kernel<%d,%d>+attn_bwd_dq_kernel", DH, NKT);
+  me_set_kernel(nm);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { me_set_hip_error("me_attn_bwd", (int)e); return ME_EHIP; }
   return ME_OK;
@@ -440,6 +442,12 @@ extern "C" int me_attn_bwd(const me_attn_bwd_args* a, void* stream) {
   if (a->n_items <= 0 || a->n_kv_items <= 0 || a->nq <= 0 || a->nk <= 0 || a->heads <= 0 || a->nseg < 1 || a->nseg > 3) { me_set_error("me_attn_bwd: bad sizes"); return ME_EINVAL; }
   if (a->ldq % 8 || a->ldk % 8 || a->ldv % 8 || a->ldo % 8 || a->lddo % 4 || a->lddq % 4 || a->lddk % 4 || a->lddv % 4) {
     me_set_error("me_attn_bwd: row strides must be multiples of 8 (fp16 tensors) / 4 (fp32 gradients)");
+    return ME_EINVAL;
+  }
+  // rows narrower than heads * dh would overlap: two blocks would then accumulate into one dQ / dK / dV element
+  const int C = a->heads * a->dh;
+  if (a->ldq < C || a->ldk < C || a->ldv < C || a->ldo < C || a->lddo < C || a->lddq < C || a->lddk < C || a->lddv < C) {
+    me_set_error("me_attn_bwd: row strides must cover heads * dh columns");
     return ME_EINVAL;
   }
   if (((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V | (uintptr_t)a->O | (uintptr_t)a->dO | (uintptr_t)a->dQ | (uintptr_t)a->dK | (uintptr_t)a->dV) & 15) {

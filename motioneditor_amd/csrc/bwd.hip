@@ -9,6 +9,7 @@
 
 extern "C" void me_set_error(const char* msg);
 extern "C" void me_set_hip_error(const char* what, int err);
+extern "C" void me_set_kernel(const char* name);
 
 namespace {
 
@@ -496,6 +497,9 @@ static int launch_tattn_bwd2(void* dq, int lddq, void* dk, int lddk, void* dv, i
   hipLaunchKernelGGL((tattn_bwd2_kernel<DH, HB>), dim3((unsigned)((long)batch * npix * (heads / HB))), dim3(HB * 64), lds, st, reinterpret_cast<const f16*>(q), ldq,
                      reinterpret_cast<const f16*>(k), ldk, reinterpret_cast<const f16*>(v), ldv, reinterpret_cast<const float*>(dout), lddo, reinterpret_cast<float*>(dq), lddq,
                      reinterpret_cast<float*>(dk), lddk, reinterpret_cast<float*>(dv), lddv, batch, frames, npix, heads, scale);
+  char nm[48];
+  snprintf(nm, sizeof(nm), "tattn_bwd2_kernel<%d,%d>", DH, HB);
+  me_set_kernel(nm);
   const hipError_t e_ = hipGetLastError();
   if (e_ != hipSuccess) { me_set_hip_error("me_tattn_bwd", (int)e_); return ME_EHIP; }
   return ME_OK;
@@ -553,6 +557,9 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__
 
 extern "C" int me_geglu_bwd(void* dpre, int32_t ldd, const void* pre, int32_t ldp, const void* dy, int32_t lddy, int64_t M, int32_t N, void* stream) {
   if (!dpre || !pre || !dy || M <= 0 || N <= 0 || N % 32) { me_set_error("me_geglu_bwd: bad arguments (N must be a multiple of 32)"); return ME_EINVAL; }
+  // element-wise kernel: rows must not overlap (two threads would write one dpre element) and the element types must be aligned
+  if (ldd < N || ldp < N || lddy < N / 2) { me_set_error("me_geglu_bwd: row strides must cover the row (N columns of pre and dpre, N / 2 of dy)"); return ME_EINVAL; }
+  if ((((uintptr_t)dpre | (uintptr_t)pre) & 1) || ((uintptr_t)dy & 3)) { me_set_error("me_geglu_bwd: misaligned pointer"); return ME_EINVAL; }
   (void)hipGetLastError();
   const long total = (long)M * (N / 2);
   const unsigned blocks = (unsigned)((total + 255) / 256 < 65536L * 16 ? (total + 255) / 256 : 65536L * 16);
@@ -564,6 +571,9 @@ extern "C" int me_geglu_bwd(void* dpre, int32_t ldd, const void* pre, int32_t ld
 extern "C" int me_layernorm_bwd(void* dx, int32_t lddx, const void* x, int32_t ldx, const void* gamma, const void* dy, int32_t lddy, int64_t rows, int32_t C, float eps,
                                 void* stream) {
   if (!dx || !x || !gamma || !dy || rows <= 0 || C <= 0) { me_set_error("me_layernorm_bwd: bad arguments"); return ME_EINVAL; }
+  // the kernel reads and writes element by element: no vector alignment to ask for, but rows must not overlap and the element types must be aligned
+  if (ldx < C || lddx < C || lddy < C) { me_set_error("me_layernorm_bwd: row strides must cover C columns"); return ME_EINVAL; }
+  if ((((uintptr_t)x | (uintptr_t)gamma) & 1) || (((uintptr_t)dx | (uintptr_t)dy) & 3)) { me_set_error("me_layernorm_bwd: misaligned pointer"); return ME_EINVAL; }
   (void)hipGetLastError();
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(x), ldx,
                      reinterpret_cast<const f16*>(gamma), reinterpret_cast<const float*>(dy), lddy, reinterpret_cast<float*>(dx), lddx, (long)rows, C, eps);
@@ -593,9 +603,17 @@ extern "C" int64_t me_groupnorm_bwd_scratch_bytes(int32_t rows, int32_t rows_per
 
 extern "C" int me_groupnorm_bwd(void* dx, int32_t lddx, const void* x, int32_t ldx, const void* gamma, const void* beta, const void* dy, int32_t lddy, int64_t rows,
                                 int32_t rows_per_group, int32_t C, int32_t groups, float eps, int32_t silu, void* scratch, void* stream) {
-  if (!dx || !x || !gamma || !beta || !dy || !scratch || rows <= 0 || rows_per_group <= 0 || rows % rows_per_group || groups <= 0 || groups > 64 || C % groups || C % 8 ||
-      C > 2560 || ldx % 8 || lddx % 4 || lddy % 4 || (((uintptr_t)dx | (uintptr_t)x | (uintptr_t)dy | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)scratch) & 15)) {
-    me_set_error("me_groupnorm_bwd: bad arguments (C % 8 == 0, C <= 2560, aligned pointers, strides multiples of 8 / 4)");
+  if (!dx || !x || !gamma || !beta || !dy || !scratch || rows <= 0 || rows_per_group <= 0 || rows % rows_per_group) {
+    me_set_error("me_groupnorm_bwd: bad arguments (null pointer, or rows not a positive multiple of rows_per_group)");
+    return ME_EINVAL;
+  }
+  if (groups <= 0 || groups > 64 || C <= 0 || C % groups || C % 8 || C > 2560) {
+    me_set_error("me_groupnorm_bwd: bad channels (1 <= groups <= 64, C a multiple of groups and of 8, C <= 2560)");
+    return ME_EINVAL;
+  }
+  if (ldx % 8 || lddx % 4 || lddy % 4) { me_set_error("me_groupnorm_bwd: row strides must be multiples of 8 (x) / 4 (dx, dy)"); return ME_EINVAL; }
+  if (((uintptr_t)dx | (uintptr_t)x | (uintptr_t)dy | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)scratch) & 15) {
+    me_set_error("me_groupnorm_bwd: misaligned pointer");
     return ME_EINVAL;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -647,6 +665,14 @@ extern "C" int me_tattn_bwd(void* dq, int32_t lddq, void* dk, int32_t lddk, void
     me_set_error("me_tattn_bwd: bad arguments (frames <= 64)");
     return ME_EINVAL;
   }
+  if (dh != 40 && dh != 80 && dh != 160) { me_set_error("me_tattn_bwd: head dim must be 40, 80 or 160"); return ME_EINVAL; }
+  {   // every kernel walks heads * dh columns of each row: a narrower row stride would make rows overlap (and the gradient rows race)
+    const long Cc = (long)heads * dh;
+    if (ldq < Cc || ldk < Cc || ldv < Cc || lddo < Cc || lddq < Cc || lddk < Cc || lddv < Cc) {
+      me_set_error("me_tattn_bwd: row strides must cover heads * dh columns");
+      return ME_EINVAL;
+    }
+  }
   {   // the lane-parallel kernel: frames <= 32, 16-byte aligned rows, heads a multiple of the heads per block
     static const bool v2 = !(getenv("ME_TATTN_BWD2") && atoi(getenv("ME_TATTN_BWD2")) == 0);
     const bool al = !((ldq | ldk | ldv) % 8) && !((lddo | lddq | lddk | lddv) % 4) &&
@@ -676,6 +702,7 @@ extern "C" int me_tattn_bwd(void* dq, int32_t lddq, void* dk, int32_t lddk, void
   hipLaunchKernelGGL(tattn_bwd_kernel, dim3((unsigned)((long)batch * npix * heads)), dim3(64), lds, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f16*>(q), ldq,
                      reinterpret_cast<const f16*>(k), ldk, reinterpret_cast<const f16*>(v), ldv, reinterpret_cast<const float*>(dout), lddo, reinterpret_cast<float*>(dq), lddq,
                      reinterpret_cast<float*>(dk), lddk, reinterpret_cast<float*>(dv), lddv, batch, frames, npix, heads, dh, scale);
+  me_set_kernel("tattn_bwd_kernel");
   ME_BWD_LAUNCH_CHECK("me_tattn_bwd")
 }
 

@@ -265,17 +265,26 @@ __global__ __launch_bounds__(256) void grad_acc_kernel(float* dst, int lddst, co
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// sum of squares and largest magnitude of an fp32 vector: out = {sum x^2, max |x|}; fixed-order two-stage reduction
+// sum of squares and largest magnitude of an fp32 vector: out = {sum x^2, max |x|}; fixed-order two-stage reduction.  A NaN anywhere in x makes
+// BOTH outputs NaN, an inf (and no NaN) makes both +inf (include/motioned.h)
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int SS_BLOCKS = 1024;
+// The larger of two magnitudes (sign bit clear), NaN winning over everything: on such values the order of the bit patterns is the order of the
+// numbers, with +inf above every finite value and every NaN above +inf.  fmaxf would DROP a NaN -- and max |x| is what the loss-scale selection and
+// the trainers' skipped-step test ask "was every gradient finite?".
+__device__ __forceinline__ float absmax_nan(float a, float b) {
+  const unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
+  return __uint_as_float(ua > ub ? ua : ub);
+}
 __device__ __forceinline__ void block_reduce2(float& s, float& m, float (*red)[2]) {
   s = wave_sum(s);
-  m = wave_max(m);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = absmax_nan(m, __shfl_xor(m, o, 64));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) { red[wave][0] = s; red[wave][1] = m; }
   __syncthreads();
   s = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-  m = fmaxf(fmaxf(red[0][1], red[1][1]), fmaxf(red[2][1], red[3][1]));
+  m = absmax_nan(absmax_nan(red[0][1], red[1][1]), absmax_nan(red[2][1], red[3][1]));
 }
 __global__ __launch_bounds__(256) void sumsq_part_kernel(const float* __restrict__ x, long n, float* __restrict__ work) {
   __shared__ float red[4][2];
@@ -284,7 +293,7 @@ __global__ __launch_bounds__(256) void sumsq_part_kernel(const float* __restrict
   for (long i = i0 + threadIdx.x; i < i1; i += 256) {
     const float v = x[i];
     s += v * v;
-    m = fmaxf(m, fabsf(v));
+    m = absmax_nan(m, fabsf(v));
   }
   block_reduce2(s, m, red);
   if (threadIdx.x == 0) { work[2 * blockIdx.x] = s; work[2 * blockIdx.x + 1] = m; }
@@ -294,7 +303,7 @@ __global__ __launch_bounds__(256) void sumsq_fold_kernel(const float* __restrict
   float s = 0.f, m = 0.f;
   for (int i = threadIdx.x; i < SS_BLOCKS; i += 256) {   // thread t adds partials t, t + 256, ... in order
     s += work[2 * i];
-    m = fmaxf(m, work[2 * i + 1]);
+    m = absmax_nan(m, work[2 * i + 1]);
   }
   block_reduce2(s, m, red);
   if (threadIdx.x == 0) { out[0] = s; out[1] = m; }
@@ -474,6 +483,8 @@ extern "C" int64_t me_colsum_work_bytes(int32_t N) { return N > 0 ? (int64_t)CS_
 
 extern "C" int me_colsum(float* out, const void* dY, int32_t lddy, int32_t dy_is_f16, int64_t M, int32_t N, float alpha, float* work, void* stream) {
   if (!out || !dY || !work || M <= 0 || N <= 0) { me_set_error("me_colsum: bad arguments"); return ME_EINVAL; }
+  if (lddy < N) { me_set_error("me_colsum: row stride must cover N columns"); return ME_EINVAL; }
+  if (((uintptr_t)dY & (dy_is_f16 ? 1 : 3)) || (((uintptr_t)out | (uintptr_t)work) & 3)) { me_set_error("me_colsum: misaligned pointer"); return ME_EINVAL; }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   (void)hipGetLastError();
   hipLaunchKernelGGL(colsum_part_f32_kernel, dim3((unsigned)((N + 255) / 256), CS_RS), dim3(256), 0, st, dY, lddy, dy_is_f16, (long)M, N, work);

@@ -431,6 +431,7 @@ def layernorm_bwd_params(x, dy, *, dgamma=None, dbeta=None, eps=1e-5):
 
 
 def sumsq_absmax(x, out=None):
+    # include/motioned.h: a NaN anywhere in x makes BOTH outputs NaN, an inf (and no NaN) both +inf -- torch's max propagates NaN, as me_sumsq_absmax does
     r = torch.stack([(x.double() ** 2).sum().float(), x.abs().max().float()])
     if out is not None:
         out.copy_(r)

@@ -169,3 +169,47 @@ def test_edited_launch_item_order_is_a_pairwise_interleaving_permutation():
         assert [o for o in order if o % (2 * f) < f] == sorted(o for o in order if o % (2 * f) < f)   # frames ascend inside a pair
     si, _ = segments.prev_cur(4, 24, "cpu")
     assert si.data_ptr() not in segments.ITEM_ORDER
+
+
+# ------------------------------------------------------------------ the argument contract of the backward ABI (tests/bwd_abi.py)
+import bwd_abi  # noqa: E402
+
+
+@pytest.mark.parametrize("entry,label", bwd_abi.violation_ids(), ids=lambda v: str(v).replace(" ", "-"))
+def test_backward_abi_refuses_a_violating_call_on_the_host(entry, label):
+    """One call per documented constraint of me_gemm_dw, me_attn_bwd, me_tattn_bwd, me_groupnorm_bwd, me_layernorm_bwd, me_geglu_bwd, me_softmax_bwd_rows,
+    me_colsum, me_sumsq_absmax and me_adamw that violates it: ME_EINVAL with a message that names the entry point and the constraint.  The pointers are fake
+    (aligned numbers no kernel could run on): a call that slipped through the host checks would reach the launch and come back ME_EHIP here, never ME_EINVAL.
+    With a device present a slipped call would launch on those numbers, so the test stands aside there: tests/test_bwd_sweep_gpu.py sends the same table with
+    sentinel-filled device buffers."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a device is present: the same violations run on real buffers in tests/test_bwd_sweep_gpu.py")
+    from motioneditor_amd import capi
+    L = capi.lib()
+    spec = bwd_abi.entries(L)[entry]
+    overrides, needle = next((o, n) for lab, o, n in spec[2] if lab == label)
+    fake = {}
+
+    def ptr(name, nbytes):
+        return fake.setdefault(name, 0x100000 * (len(fake) + 1))
+    rc = bwd_abi.call(L, capi, entry, spec, overrides, ptr)
+    msg = L.me_last_error().decode()
+    assert rc == capi.ME_EINVAL, f"{entry} ({label}): status {rc}, message {msg!r}"
+    assert msg.startswith(entry + ":") and needle in msg, f"{entry} ({label}): message {msg!r} should name the entry point and hold {needle!r}"
+
+
+def test_backward_abi_table_names_every_entry_point_of_the_contract():
+    from motioneditor_amd import capi
+    want = {"me_gemm_dw", "me_attn_bwd", "me_tattn_bwd", "me_groupnorm_bwd", "me_layernorm_bwd", "me_geglu_bwd", "me_softmax_bwd_rows", "me_colsum", "me_sumsq_absmax", "me_adamw"}
+    table = bwd_abi.entries(capi.lib())
+    assert set(table) == want and want <= set(capi.SYMBOLS)
+    for entry, (kind, args, violations) in table.items():
+        labels = [v[0] for v in violations]
+        assert len(labels) == len(set(labels)) and len(labels) >= 4, entry
+        names = {a[0] for a in args}
+        assert all(set(o) <= names for _, o, _ in violations), entry
+        nulled = {n for _, o, _ in violations for n, v in o.items() if v == bwd_abi.NULL}
+        assert nulled, entry
+        if kind == "args":
+            assert len(args) + 1 == len(capi.SYMBOLS[entry][1]), entry           # the legal call matches the C signature (+ the stream)

@@ -898,7 +898,7 @@ def test_guard_attention_bwd(ops, kind, dh, nq, nk, f):
     ins.update(out=E(fwd["out"]), lse=V(fwd["lse"]), dout=E(dout), dq=E(w0[0]), dk=E(w0[1]), dv=E(w0[2]))
     got = run_guarded(lambda: ops.attention_bwd(ins["q"], ins["k"], ins["v"], ins["out"], ins["dout"], dq=ins["dq"], dk=ins["dk"], dv=ins["dv"], lse=ins["lse"], seg_item=sic, seg_mode=smc,
                                                 **args), ins, {}, inout=["dq", "dk", "dv"])
-    kernel_is(ops, "attn_bwd_dkv_kernel+attn_bwd_dq_kernel")
+    kernel_is(ops, f"attn_bwd_dkv_kernel<{dh},{1 if dh == 160 else 2}>+attn_bwd_dq_kernel")      # keys per block = 64 * NKT: 2 for dh 40 / 80, 1 for dh 160
     want = [t.clone() for t in w0]
     emu.attention_bwd(q, k, v, None, dout, dq=want[0], dk=want[1], dv=want[2], seg_item=si, seg_mode=sm, **args)
     for n, b, z in zip(("dq", "dk", "dv"), want, w0):

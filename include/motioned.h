@@ -52,7 +52,7 @@ int me_device_info(int* cus, int* lds_bytes, char* arch, int arch_len);
  * (attention_2d.py:307,336), time_emb_proj (resnet_2d.py:172,211).
  */
 #define ME_GATHER_DENSE 0  /* taps = 1, src(m) = m                                                  */
-#define ME_GATHER_CONV3 1  /* taps = 9, 3x3 pad 1 over [img][Hin][Win] pixels; stride 1|2; ups 0|1|2 */
+#define ME_GATHER_CONV3 1  /* taps = 9 (16 at ups = 3), 3x3 pad 1 over [img][Hin][Win] pixels; stride 1|2; ups 0|1|2|3 */
 #define ME_GATHER_TCONV 2  /* taps = 3, k=3 pad 1 over frames inside chunks of `chunk` frames       */
 
 typedef struct me_gemm_args {
@@ -64,7 +64,12 @@ typedef struct me_gemm_args {
   int32_t gather;     /* ME_GATHER_*                                           */
   /* CONV3: M = n_img * Hout * Wout.  ups = 1: the input is read through a nearest-neighbour 2x upsample (Upsample2D folded into
    * the gather); ups = 2: through a ZERO-STUFFED 2x upsample (virtual pixel (2y, 2x) = input pixel (y, x), every other virtual
-   * pixel is zero) -- the input gradient of a stride-2 convolution is the stride-1 correlation of the zero-stuffed output gradient */
+   * pixel is zero) -- the input gradient of a stride-2 convolution is the stride-1 correlation of the zero-stuffed output gradient;
+   * ups = 3: the convolution of ups = 1 (stride 1, pad0 = 0, Hout = 2 Hin, Wout = 2 Win) run as four 2x2-tap convolutions over the low-resolution
+   * grid, one per output parity (py, px): W is fp16 [N, 16, K], middle index 4 (2 py + px) + 2 ty + tx, tap (ty, tx) of parity (py, px) reads input
+   * pixel (y + py - 1 + ty, x + px - 1 + tx) (zero outside the image) and holds the sum of the 3x3 taps that land on that pixel (1, 2 or 4 of them);
+   * output row img Hout Wout + (2y + py) Wout + 2x + px, every epilogue term indexed by that output row, as at ups = 1.  4/9 of the multiply-adds;
+   * never split along K, never the halo kernel: a sub-batch (sel_rows) is bitwise the rows of the full launch */
   int32_t Hin, Win, Hout, Wout, stride, ups;
   int32_t pad0;       /* CONV3: 0 = padding 1 on every side; 1 = no padding at the top / left, one row / column at the bottom /
                          right (diffusers Downsample2D(padding=0) of the VAE encoder: F.pad(x, (0,1,0,1)) + stride-2 conv) */

@@ -3,7 +3,8 @@
 //   C[m, n] = epilogue( sum_{tap} sum_{c < K} X[src(m, tap), c] * W[n, tap, c] )
 //
 // One kernel serves nn.Linear, 1x1 conv, 3x3 conv (stride 1/2, optional nearest-2x upsample of the
-// input folded into the gather) and the k=3 temporal conv: only the row-gather src(m, tap) differs.
+// input folded into the gather, or -- ups 3 -- run as four 2x2-tap convolutions over the low-resolution grid, one per output parity, with
+// pre-summed weights) and the k=3 temporal conv: only the row-gather src(m, tap) differs.
 // Activations are channels-last so every tap is a contiguous K-run of one source row.
 //
 // Tiling: BM x BN x 64 block tile, waves in a (BM/64) x 2 grid, each wave 64 x (BN/2) built from
@@ -78,14 +79,25 @@ struct RowInfo {
   bool valid;
 };
 
-__device__ __forceinline__ RowInfo make_row(const me_gemm_args& a, int m) {
+// ups 3 (nearest 2x folded into four 2x2-tap convolutions): the kernels see ONE output parity par = 2 py + px at a time -- me_gemm hands them
+// M = rows per parity, row m = (image, low-res pixel (y, x)) -- and tap (ty, tx) reads low-res pixel (y + py - 1 + ty, x + px - 1 + tx).
+// (ups3 is a parameter, not read from `a`: a compile-time false in the instantiations that never see the mode, so that their code stays what it was)
+__device__ __forceinline__ RowInfo make_row(const me_gemm_args& a, int m, int par = 0, bool ups3 = false) {
   RowInfo r;
   r.valid = m < a.M;
   r.base = m;
   r.y0 = 0;
   r.x0 = 0;
   if (!r.valid) return r;
-  if (a.gather == ME_GATHER_CONV3) {
+  if (ups3) {
+    const int hw = a.Hin * a.Win;
+    const int img = m / hw;
+    const int rem = m - img * hw;
+    const int y = rem / a.Win;
+    r.base = img * hw;
+    r.y0 = y + (par >> 1) - 1;
+    r.x0 = rem - y * a.Win + (par & 1) - 1;
+  } else if (a.gather == ME_GATHER_CONV3) {
     const int hw = a.Hout * a.Wout;
     const int img = m / hw;
     const int rem = m - img * hw;
@@ -103,9 +115,14 @@ __device__ __forceinline__ RowInfo make_row(const me_gemm_args& a, int m) {
 }
 
 // source row of (row, tap) or -1 when the tap falls into zero padding
-__device__ __forceinline__ int src_row(const me_gemm_args& a, const RowInfo& r, int tap) {
+__device__ __forceinline__ int src_row(const me_gemm_args& a, const RowInfo& r, int tap, bool ups3 = false) {
   if (!r.valid) return -1;
   if (a.gather == ME_GATHER_DENSE) return r.base;
+  if (ups3) {
+    const int iy = r.y0 + (tap >> 1), ix = r.x0 + (tap & 1);
+    if (iy < 0 || iy >= a.Hin || ix < 0 || ix >= a.Win) return -1;
+    return r.base + iy * a.Win + ix;
+  }
   if (a.gather == ME_GATHER_CONV3) {
     const int ky = tap / 3, kx = tap - ky * 3;
     const int iy = r.y0 + ky, ix = r.x0 + kx;
@@ -123,6 +140,12 @@ __device__ __forceinline__ int src_row(const me_gemm_args& a, const RowInfo& r, 
   if (ls >= 0 && ls < a.frames) return r.base + dt * a.npix;
   const int hb = ls < 0 ? a.halo_prev : a.halo_next;    // neighbour rank's boundary frame
   return hb < 0 ? -1 : hb + r.x0;
+}
+
+// ups 3: output row of a (valid) row of parity par -- pixel (2 y + py, 2 x + px) of its image
+__device__ __forceinline__ int out_row(const me_gemm_args& a, const RowInfo& r, int par) {
+  const int py = par >> 1, px = par & 1;
+  return r.base * 4 + (2 * (r.y0 + 1 - py) + py) * a.Wout + 2 * (r.x0 + 1 - px) + px;
 }
 
 // The bias enters as the accumulators' initial value (bias / alpha, so that alpha * acc adds exactly the bias): its
@@ -430,8 +453,10 @@ __device__ __forceinline__ void epilogue_rows(const me_gemm_args& a, f32x4 (&acc
 //   (float2 [2 wave rows][4 wave columns][GR rows], behind a block barrier), and 2 * GR threads store one (sum, sum of squares) pair per row of the
 //   tile -- a fixed order throughout.  lnx = {first row of the tile, wave row, wave column, thread id}.
 struct LnOutCtx { int m0, wr, wc, tid; char* red; };
-template <int F, int NT, int MT, int WN>
-__device__ __forceinline__ void epilogue_rowpass(const me_gemm_args& a, f32x4 (&acc)[NT][MT], int mw0, int nw0, int lane, char* scr, const LnOutCtx& lnx) {
+//   OMAP / otab (ups 3, term-free instantiation only): otab[row of the tile] = the output row of that row (an LDS table the kernel's prologue filled); nullptr: row m is output row m.
+template <int F, int NT, int MT, int WN, bool OMAP = false>
+__device__ __forceinline__ void epilogue_rowpass(const me_gemm_args& a, f32x4 (&acc)[NT][MT], int mw0, int nw0, int lane, char* scr, const LnOutCtx& lnx, const int* otab = nullptr) {
+  static_assert(!OMAP || F == 0, "the output-row map serves the term-free epilogue");
   static_assert(F >= 0 && (F & 1) == 0 && MT % 2 == 0 && WN % 16 == 0, "row-pass epilogue");
   constexpr bool has_rv = (F & 2) != 0, has_res = (F & 4) != 0, has_res2 = (F & 8) != 0;
     // a chunk = two 16-row MFMA row blocks = 32 rows x WN columns = 32 * WN / 8 16-byte pieces, IT per lane (5 at WN = 80: no masked piece)
@@ -548,7 +573,11 @@ __device__ __forceinline__ void epilogue_rowpass(const me_gemm_args& a, f32x4 (&
     for (int t = 0; t < IT; ++t) {
       const int m = mw0 + c * ROWS + prow[t];
       if (m >= a.M) continue;
-      f16* dst = C + (long)m * a.ldc + pcol[t];
+      long mo = m;
+      if constexpr (OMAP) {
+        if (otab) mo = otab[m - lnx.m0];     // (wave-uniform test)
+      }
+      f16* dst = C + mo * a.ldc + pcol[t];
       if (c2 && hoff[t] >= 0) dst = reinterpret_cast<f16*>(a.C2) + (long)m * a.c2_dh + hoff[t];
       st16(dst, d[t].u);
     }
@@ -789,7 +818,8 @@ __device__ __forceinline__ void epilogue(const me_gemm_args& a, f32x4 (&acc)[NT]
 
 // BM = 128 (4 waves, 2 blocks/CU) or 256 (8 waves, 1 block/CU).  The 256 x 320 tile halves the L2 -> LDS fill per
 // FLOP (142 vs 71 flop/byte of staged operands): the 128-row tiles measured fill-bound at ~8 TB/s for K <= 640.
-template <int BM, int BN, int STAGE, int WM = 64>
+// UPS3: the instantiations that take the folded nearest-2x convolution (ups 3, me_gemm launches nothing else on them); every other one compiles without a trace of it.
+template <int BM, int BN, int STAGE, int WM = 64, bool UPS3 = false>
 __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(const me_gemm_args a) {
   constexpr int NTHR = BM / WM * 128;  // WM rows x 2 wave columns per 64 threads
   constexpr int RSTR = NTHR / 8;  // row stride between a thread's staged rows
@@ -811,20 +841,25 @@ __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(
 
   const int nbn = (a.N + BN - 1) / BN;
   const int nbm = (a.M - a.m_off + BM - 1) / BM;   // tiles cover the rows [m_off, M)
-  const int w = xcd_remap(blockIdx.x, nbm * nbn);
-  const int tile_n = w % nbn, tile_m = w / nbn;
+  // ups 3: a.M = rows of ONE output parity; the grid holds the nbm row tiles of parity 0, then those of parity 1, ... -- a tile never mixes parities
+  constexpr bool ups3 = UPS3;
+  const int w = xcd_remap(blockIdx.x, nbm * nbn * (ups3 ? 4 : 1));
+  const int tile_n = w % nbn, tile_mp = w / nbn;
+  const int par = ups3 ? tile_mp / nbm : 0, tile_m = tile_mp - par * nbm;
   const int m0 = a.m_off + tile_m * BM, n0 = tile_n * BN;
 
+  // weight rows are [wtaps][K]; the K loop walks `taps` of them from the base (ups 3: the four folded taps of this block's parity out of 16)
+  const int taps = a.gather == ME_GATHER_CONV3 ? (ups3 ? 4 : 9) : (a.gather == ME_GATHER_TCONV ? 3 : 1);
+  const int wtaps = ups3 ? 16 : taps;
   const f16* __restrict__ X = reinterpret_cast<const f16*>(a.X);
-  const f16* __restrict__ W = reinterpret_cast<const f16*>(a.W);
+  const f16* __restrict__ W = reinterpret_cast<const f16*>(a.W) + (long)(4 * par) * a.K;
 
-  const int taps = a.gather == ME_GATHER_CONV3 ? 9 : (a.gather == ME_GATHER_TCONV ? 3 : 1);
   const int nkc = (a.K + BK - 1) / BK;
   // 3x3 convs with fewer than 64 input channels (the ControlNet conditioning embedding: 16, 32) pack (tap, channel)
   // into ONE K axis of 9 K -- the weights [N][9][K] are contiguous in exactly that order -- instead of nine 64-wide
   // slabs that are 75 % / 50 % zero padding: 3 / 5 slabs instead of 9.  A lane's 16-byte chunk then belongs to
   // the tap (slab * 64 + chunk offset) / K, different lanes gather different taps of their rows.
-  const bool packk = STAGE == STAGE_GLDS && a.gather == ME_GATHER_CONV3 && a.K < BK && BK % a.K == 0;   // (STAGE_BUF is only launched with K % 64 == 0)
+  const bool packk = STAGE == STAGE_GLDS && a.gather == ME_GATHER_CONV3 && !ups3 && a.K < BK && BK % a.K == 0;   // (STAGE_BUF is only launched with K % 64 == 0)
   const int nit = packk ? (9 * a.K + BK - 1) / BK : taps * nkc;
 
   // staging assignment
@@ -842,7 +877,7 @@ __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(
 
   RowInfo rinfo[XROWS];
 #pragma unroll
-  for (int i = 0; i < XROWS; ++i) rinfo[i] = make_row(a, m0 + srow + RSTR * i);
+  for (int i = 0; i < XROWS; ++i) rinfo[i] = make_row(a, m0 + srow + RSTR * i, par, ups3);
 
   long xoff[XROWS];  // element offset of the source row for the current tap, or -1
   int cur_tap = -1;
@@ -851,7 +886,7 @@ __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(
       cur_tap = tap;
 #pragma unroll
       for (int i = 0; i < XROWS; ++i) {
-        const int s = src_row(a, rinfo[i], tap);
+        const int s = src_row(a, rinfo[i], tap, ups3);
         xoff[i] = s < 0 ? -1L : (long)s * a.ldx;
       }
     }
@@ -902,18 +937,18 @@ __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(
     constexpr unsigned OOB = 0x80000000u;
     // X window: rows are addressed relative to the block's lowest source row, so the 32-bit offsets stay below 2 GB on any tensor
     long brow = m0;
-    if (a.gather == ME_GATHER_CONV3) brow = (long)(m0 / (a.Hout * a.Wout)) * a.Hin * a.Win;
+    if (a.gather == ME_GATHER_CONV3) brow = (long)(m0 / (ups3 ? a.Hin * a.Win : a.Hout * a.Wout)) * a.Hin * a.Win;
     else if (a.gather == ME_GATHER_TCONV) brow = m0 > a.npix ? m0 - a.npix : 0;
     const auto xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(X + brow * a.ldx), 0, OOB, 0x00020000);
     const int wrows = min(a.N - n0, BN);
-    const auto wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(W + (long)n0 * taps * a.K), 0, (unsigned)((long)wrows * taps * a.K * 2), 0x00020000);
+    const auto wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(W + (long)n0 * wtaps * a.K), 0, (unsigned)(((long)(wrows - 1) * wtaps + taps) * a.K * 2), 0x00020000);
     unsigned xo[XROWS], wo[WROWS];
 #pragma unroll
-    for (int i = 0; i < WROWS; ++i) wo[i] = (unsigned)(((long)(srow + RSTR * i) * taps * a.K + scol) * 2);
+    for (int i = 0; i < WROWS; ++i) wo[i] = (unsigned)(((long)(srow + RSTR * i) * wtaps * a.K + scol) * 2);
     auto set_tap_off = [&](int tap) {
 #pragma unroll
       for (int i = 0; i < XROWS; ++i) {
-        const int sr = src_row(a, rinfo[i], tap);
+        const int sr = src_row(a, rinfo[i], tap, ups3);
         xo[i] = sr < 0 ? OOB : (unsigned)(((long)(sr - brow) * a.ldx + scol) * 2);
       }
     };
@@ -981,7 +1016,7 @@ __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(
 #pragma unroll
       for (int i = 0; i < WROWS; ++i) {
         const int n = n0 + srow + RSTR * i;
-        const f16* src = (kok && n < a.N) ? W + (long)n * taps * a.K + wk : zsrc;
+        const f16* src = (kok && n < a.N) ? W + (long)n * wtaps * a.K + wk : zsrc;
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(dw + i * (RSTR * 128)), 16, 0, 0);
       }
     };
@@ -1005,7 +1040,7 @@ __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(
 #pragma unroll
       for (int i = 0; i < WROWS; ++i) {
         const int n = n0 + srow + RSTR * i;
-        rw[i] = (kok && n < a.N) ? ldg128(W + ((long)n * taps + tap) * a.K + c) : zero128();
+        rw[i] = (kok && n < a.N) ? ldg128(W + ((long)n * wtaps + tap) * a.K + c) : zero128();
       }
     };
     auto sstore = [&](int buf) {
@@ -1033,10 +1068,11 @@ __global__ __launch_bounds__(BM / WM * 128, WM == 128 ? 1 : 2) void gemm_kernel(
   const int ncols = a.geglu ? BN / 2 : BN;            // output columns of this block
   const int Nout = a.geglu ? a.N / 2 : a.N;
   constexpr bool CFITS = (size_t)BM * (BN + 8) <= (size_t)2 * (BM + BN) * LD;   // the C tile fits the staging buffers
-  const bool wide_store = CFITS && (Nout % 8 == 0) && (a.ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(a.C) & 15) == 0) && !a.C2;
+  const bool wide_store = CFITS && (Nout % 8 == 0) && (a.ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(a.C) & 15) == 0) && !a.C2 && !ups3;   // (ups 3: a tile's output rows are not consecutive)
   auto rowfn = [&](int i) {
     const int m = m0 + wm * WM + i * 16 + (lane & 15);
-    return m < a.M ? m : -1;
+    if (m >= a.M) return -1;
+    return ups3 ? out_row(a, make_row(a, m, par, true), par) : m;
   };
   if (!wide_store) {
     epilogue<NT, MT, WN>(a, acc, rowfn, m0, n0, wn, lane, nullptr, 0);
@@ -1202,8 +1238,11 @@ __global__ __launch_bounds__(512, 2) void conv3_halo_kernel(const me_gemm_args a
 // res, rowvec + res, res + res2; BN = 256: 0 = the GEGLU row pass) or, EPI = -1, every direct epilogue behind run-time tests.  One kernel with all of them
 // behind a switch carried 530 spilled VGPRs (hipcc hoists the lane-constant address arithmetic of EVERY variant above the K loop, where 160 accumulators
 // and 56 fragment registers leave room for none of it); one variant per instantiation: 0 (22 for res + res2).  Same arithmetic, bitwise the same output.
-template <int BM, int BN, bool GATHER, int EPI>
+// UPS3: the instantiations that take the folded nearest-2x convolution (ups 3; EPI 0 and -1 only, me_gemm launches nothing else on them) -- as for gemm_kernel,
+// every other instantiation compiles without a trace of the mode.
+template <int BM, int BN, bool GATHER, int EPI, bool UPS3 = false>
 __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const me_gemm_args a) {
+  static_assert(!UPS3 || (GATHER && BN == 320 && EPI <= 0), "ups 3: gather kernels, term-free row pass or direct epilogues");
   // BM = 256, or 192 for grids whose 256-row tiles would leave the last block round half empty (M = 24576 x N = 1280: 384 tiles = 1.5 rounds of
   // the 256 CUs, 512 tiles of 192 rows = 2): wave tile GR x WN with GR = BM / 2 rows per wave group, A halves of HALF = GR / 2 rows.
   constexpr int WN = BN / 4, NT = WN / 16, NT0 = (NT + 1) / 2, NT1 = NT / 2;
@@ -1220,17 +1259,22 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const me_gemm_args a) {
 
   const int nbn = (a.N + BN - 1) / BN;
   const int nbm = (a.M - a.m_off + BM - 1) / BM;   // tiles cover the rows [m_off, M)
-  const int w = xcd_remap(blockIdx.x, nbm * nbn);
+  constexpr bool ups3 = UPS3;   // a.M = rows of one output parity, four parities of nbm row tiles each (gemm_kernel)
+  const int nbmp = ups3 ? 4 * nbm : nbm;
+  const int w = xcd_remap(blockIdx.x, nbmp * nbn);
   // tile order inside an XCD's contiguous run: column tiles fastest (default: the nbn tiles of a row block run side by side and share its A rows in L2) or, with
   // TILEORDER_FLAG (experiment, ME_GEMM_TILE_ORDER=1), row blocks fastest: 32 row blocks of ONE column tile at a time share its weight slabs
   int tile_n, tile_m;
-  if (a.splits_ & TILEORDER_FLAG) { tile_m = w % nbm; tile_n = w / nbm; }
+  if (a.splits_ & TILEORDER_FLAG) { tile_m = w % nbmp; tile_n = w / nbmp; }
   else { tile_n = w % nbn; tile_m = w / nbn; }
+  const int par = ups3 ? tile_m / nbm : 0;
+  tile_m -= par * nbm;
   const int m0 = a.m_off + tile_m * BM, n0 = tile_n * BN;
 
   const f16* __restrict__ X = reinterpret_cast<const f16*>(a.X);
-  const f16* __restrict__ W = reinterpret_cast<const f16*>(a.W);
-  const int taps = !GATHER ? 1 : (a.gather == ME_GATHER_CONV3 ? 9 : (a.gather == ME_GATHER_TCONV ? 3 : 1));
+  const int taps = !GATHER ? 1 : (a.gather == ME_GATHER_CONV3 ? (ups3 ? 4 : 9) : (a.gather == ME_GATHER_TCONV ? 3 : 1));
+  const int wtaps = ups3 ? 16 : taps;   // weight rows are [wtaps][K]; ups 3: the K loop walks the four folded taps of this block's parity
+  const f16* __restrict__ W = reinterpret_cast<const f16*>(a.W) + (long)(4 * par) * a.K;
   const int nkc = a.K / BK;
   const int nit = taps * nkc;
 
@@ -1238,12 +1282,12 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const me_gemm_args a) {
   constexpr unsigned OOB = 0x80000000u;
   long brow = m0;
   if (GATHER) {
-    if (a.gather == ME_GATHER_CONV3) brow = (long)(m0 / (a.Hout * a.Wout)) * a.Hin * a.Win;
+    if (a.gather == ME_GATHER_CONV3) brow = (long)(m0 / (ups3 ? a.Hin * a.Win : a.Hout * a.Wout)) * a.Hin * a.Win;
     else if (a.gather == ME_GATHER_TCONV) brow = m0 > a.npix ? m0 - a.npix : 0;
   }
   const auto xsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(X + brow * a.ldx), 0, OOB, 0x00020000);
   const int wrows = min(a.N - n0, BN);
-  const auto wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(W + (long)n0 * taps * a.K), 0, (unsigned)((long)wrows * taps * a.K * 2), 0x00020000);
+  const auto wsrd = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(W + (long)n0 * wtaps * a.K), 0, (unsigned)(((long)(wrows - 1) * wtaps + taps) * a.K * 2), 0x00020000);
 
   // DMA lane mapping as in gemm_kernel: one wave instruction = 8 LDS rows x 128 B, lane -> row + lane / 8, 16-byte slot lane % 8
   // holding source chunk (lane % 8) ^ ((row >> 1) & 7); every piece of this wave starts on a row whose bit 3 is wave & 1
@@ -1276,11 +1320,12 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const me_gemm_args a) {
   unsigned xo[2][2];
   if constexpr (GATHER) {
     const int r = tid & 255;
-    const RowInfo ri = make_row(a, r < BM ? m0 + r : a.M);
+    const RowInfo ri = make_row(a, r < BM ? m0 + r : a.M, par, ups3);
     for (int tap = tid >> 8; tap < taps; tap += 2) {
-      const int sr = src_row(a, ri, tap);
+      const int sr = src_row(a, ri, tap, ups3);
       tab[tap * 256 + r] = sr < 0 ? OOB : (unsigned)((long)(sr - brow) * a.ldx * 2);
     }
+    if (ups3 && tid < 256) tab[4 * 256 + r] = ri.valid ? (unsigned)out_row(a, ri, par) : ~0u;   // behind the four tap rows: the tile's output rows, for the epilogue
     __syncthreads();
   } else {
 #pragma unroll
@@ -1293,9 +1338,9 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const me_gemm_args a) {
   }
   unsigned wo0[NT0], wo1[NT1];
 #pragma unroll
-  for (int i = 0; i < NT0; ++i) wo0[i] = (unsigned)(((long)(rB0[i] + prow) * taps * a.K + scol) * 2);
+  for (int i = 0; i < NT0; ++i) wo0[i] = (unsigned)(((long)(rB0[i] + prow) * wtaps * a.K + scol) * 2);
 #pragma unroll
-  for (int i = 0; i < NT1; ++i) wo1[i] = (unsigned)(((long)(rB1[i] + prow) * taps * a.K + scol) * 2);
+  for (int i = 0; i < NT1; ++i) wo1[i] = (unsigned)(((long)(rB1[i] + prow) * wtaps * a.K + scol) * 2);
 
   // issue cursors, one per part: tl = K tile the next issue of the part belongs to.  The weight rows are [taps][K] contiguous and K is a
   // multiple of 64, so a B part's scalar offset is simply tl * 128 bytes; the A parts of a gather also track (tap, k chunk).
@@ -1487,10 +1532,12 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(const me_gemm_args a) {
     char* scr = smem + wave * (32 * (WN * 2 + 16));
     const int mw0 = m0 + wr * GR, nw0 = n0 + wc * WN;
     const LnOutCtx lnx = {m0, wr, wc, tid, smem + 8 * (32 * (WN * 2 + 16))};    // `red` (8 KB) behind the eight scratches
-    return epilogue_rowpass<EPI, NT, MT, WN>(a, acc, mw0, nw0, lane, scr, lnx);
+    // (ups 3: me_gemm sends the term-free launches here and everything else to the direct epilogues; the table lies behind the staging buffers)
+    return epilogue_rowpass<EPI, NT, MT, WN, UPS3 && EPI == 0>(a, acc, mw0, nw0, lane, scr, lnx, ups3 ? reinterpret_cast<const int*>(tab + 4 * 256) : nullptr);
   } else {
     auto rowfn = [&](int i) {
       const int m = m0 + wr * GR + i * 16 + (lane & 15);
+      if constexpr (UPS3) return (int)tab[4 * 256 + wr * GR + i * 16 + (lane & 15)];   // -1 past M
       return m < a.M ? m : -1;
     };
     epilogue<NT, MT, WN>(a, acc, rowfn, m0, n0, wc, lane, nullptr, 0);
@@ -1559,7 +1606,7 @@ int choose_split(const me_gemm_args* a, long blocks, int nit) {
   // N >= 1280 only (the 16 x 16- and 8 x 8-latent levels): a split changes the fp32 summation order, and the level-0 / level-1 launches must give
   // the same rows whatever the batch size -- the UNet graph runs its first blocks on half the batch (classifier-free-guidance prefix) and the
   // step has to stay bitwise the same.  (A 20-tile K loop measured slower split than whole: 32 tiles at least.)
-  if (a->geglu || a->K % 64 || a->N < 1280 || blocks >= split_below() || nit < 32 || a->C2 || a->m_off || a->ln_stats) return 1;
+  if (a->geglu || a->K % 64 || a->N < 1280 || blocks >= split_below() || nit < 32 || a->C2 || a->m_off || a->ln_stats || (a->gather == ME_GATHER_CONV3 && a->ups == 3)) return 1;   // (ups 3: never split -- the partial-sum pass knows no output-row map)
   int S = (int)((640 + blocks - 1) / blocks);
   if (S > 4) S = 4;
   if (S > nit / 4) S = nit / 4;
@@ -1575,13 +1622,12 @@ int stage_impl() {
   return impl;
 }
 
-long big_min_blocks() {   // ME_GEMM_BIG_MIN: smallest grid (in 256x320 blocks) that gets the big tile; 0 disables nothing, huge disables it
-  static long v = -1;
-  if (v < 0) {
-    const char* e = getenv("ME_GEMM_BIG_MIN");
-    v = e ? atol(e) : 512;
-  }
-  return v;
+// Which switches are read when.  PER CALL (one getenv per me_gemm; tests and tools/kbench.py flip them inside one process): ME_GEMM_BIG_MIN, ME_GEMM_8P, ME_GEMM_ROWEPI,
+// ME_GEMM_8P_192, ME_GEMM_8P_128, ME_GEMM_192_MINK, ME_GEMM_GEGLU_MIN, ME_GEMM_N64_BELOW, ME_GEMM_SPLITK.  ONCE per process (A/B builds of a whole run): ME_GEMM_STAGE,
+// ME_CONV_HALO_MIN, ME_CONV_HALO, ME_GEMM_BUF, ME_GEMM_TILE_ORDER, ME_GEMM_TILE160.
+long big_min_blocks() {   // ME_GEMM_BIG_MIN: smallest grid (in 256x320 blocks) that gets the big tile; 0 disables nothing, huge disables it (per call since round 7: the ups = 3 tests force both 8-phase kernels)
+  const char* e = getenv("ME_GEMM_BIG_MIN");
+  return e ? atol(e) : 512;
 }
 
 long halo_min_blocks() {   // ME_CONV_HALO_MIN: smallest grid (16x16-pixel patches x 320-channel tiles) that takes the halo kernel
@@ -1674,7 +1720,7 @@ extern "C" const char* me_last_kernel(void);
 
 static thread_local bool g_ln_fused = false;   // the launch me_gemm just made writes me_gemm_args.ln_out from its own epilogue (else me_gemm appends me_ln_stats)
 
-template <int BM, int BN, int STAGE, int WM = 64>
+template <int BM, int BN, int STAGE, int WM = 64, bool UPS3 = false>
 static int launch_gemm(const me_gemm_args* a, hipStream_t st) {
   const size_t lds = (size_t)2 * (BM + BN) * (STAGE != STAGE_REG ? BK : BK + 8) * sizeof(f16);
   static bool attr_set_dev[64] = {};   // the attribute is per device: a process that drives several GPUs sets it on each
@@ -1682,13 +1728,15 @@ static int launch_gemm(const me_gemm_args* a, hipStream_t st) {
   (void)hipGetDevice(&dev_id);
   bool& attr_set = attr_set_dev[dev_id & 63];
   if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, STAGE, WM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_kernel<BM, BN, STAGE, WM, UPS3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
       me_set_error("me_gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
       return ME_EHIP;
     }
     attr_set = true;
   }
-  const int nbm = (a->M - a->m_off + BM - 1) / BM, nbn = (a->N + BN - 1) / BN;
+  constexpr int pm = UPS3 ? 4 : 1;   // ups 3: a->M = rows per output parity (gemm_dispatch), four parities of row tiles
+  if (UPS3 != (a->gather == ME_GATHER_CONV3 && a->ups == 3)) { me_set_error("me_gemm: internal: ups = 3 launch on the wrong instantiation"); return ME_EINVAL; }
+  const int nbm = (a->M - a->m_off + BM - 1) / BM * pm, nbn = (a->N + BN - 1) / BN;
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   me_gemm_args b = *a;
   b.splits_ = 0;
@@ -1703,11 +1751,11 @@ static int launch_gemm(const me_gemm_args* a, hipStream_t st) {
   }
   if (S > 1) {
     b.splits_ = S;
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, STAGE, WM>), dim3(nbm * nbn, S), dim3(BM / WM * 128), lds, st, b);
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, STAGE, WM, UPS3>), dim3(nbm * nbn, S), dim3(BM / WM * 128), lds, st, b);
     const long vec = (long)a->M * (a->N / 4);
     hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)((vec + 255) / 256 < 4096 ? (vec + 255) / 256 : 4096)), dim3(256), 0, st, b);
   } else {
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, STAGE, WM>), dim3(nbm * nbn), dim3(BM / WM * 128), lds, st, b);
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, STAGE, WM, UPS3>), dim3(nbm * nbn), dim3(BM / WM * 128), lds, st, b);
   }
   {
     char nm[64];
@@ -1721,7 +1769,7 @@ static int launch_gemm(const me_gemm_args* a, hipStream_t st) {
   return ME_OK;
 }
 
-template <int BM, int BN, bool GATHER, int EPI>
+template <int BM, int BN, bool GATHER, int EPI, bool UPS3 = false>
 static int launch_gemm8p_epi(const me_gemm_args& b, hipStream_t st) {
   const int lds = 2 * (BM + BN) * 128 + (GATHER ? 9 * 256 * 4 : (EPI == 0 ? LN_LDS_BYTES : 0));   // (dense, term-free: room for the LayerNorm fold's operands)
   static bool attr_set_dev[64] = {};
@@ -1729,14 +1777,15 @@ static int launch_gemm8p_epi(const me_gemm_args& b, hipStream_t st) {
   (void)hipGetDevice(&dev_id);
   bool& attr_set = attr_set_dev[dev_id & 63];
   if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<BM, BN, GATHER, EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel<BM, BN, GATHER, EPI, UPS3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
       me_set_error("me_gemm: hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
       return ME_EHIP;
     }
     attr_set = true;
   }
-  const int nbm = (b.M - b.m_off + BM - 1) / BM, nbn = (b.N + BN - 1) / BN;
-  hipLaunchKernelGGL((gemm8p_kernel<BM, BN, GATHER, EPI>), dim3(nbm * nbn), dim3(512), lds, st, b);
+  constexpr int pm = UPS3 ? 4 : 1;
+  const int nbm = (b.M - b.m_off + BM - 1) / BM * pm, nbn = (b.N + BN - 1) / BN;
+  hipLaunchKernelGGL((gemm8p_kernel<BM, BN, GATHER, EPI, UPS3>), dim3(nbm * nbn), dim3(512), lds, st, b);
   return ME_OK;
 }
 
@@ -1749,7 +1798,8 @@ static int launch_gemm8p(const me_gemm_args* a, hipStream_t st) {
   {   // row-contiguous epilogue (epilogue_rowpass): 16-byte pieces of every tensor it touches, one of the specialised term sets
     auto al = [](const void* p, int ld) { return p == nullptr || (ld % 8 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0); };
     const int f = (a->rowvec ? 2 : 0) | (a->res ? 4 : 0) | (a->res2 ? 8 : 0);
-    if (BN == 320 && row_epilogue() && !a->geglu && a->act == 0 && a->N % 320 == 0 && (f == 0 || f == 2 || f == 4 || f == 6 || f == 12) && al(a->C, a->ldc) &&
+    const bool ups3 = a->gather == ME_GATHER_CONV3 && a->ups == 3;   // its output rows are scattered: only the term-free row pass carries the map
+    if (BN == 320 && !(ups3 && f != 0) && row_epilogue() && !a->geglu && a->act == 0 && a->N % 320 == 0 && (f == 0 || f == 2 || f == 4 || f == 6 || f == 12) && al(a->C, a->ldc) &&
         al(a->rowvec, a->ldrv) && al(a->res, a->ldr) && al(a->res2, a->ldr2) && (!a->C2 || f == 0))
       epi = f;
     if (tile_order_exp()) b.splits_ |= TILEORDER_FLAG;
@@ -1759,7 +1809,11 @@ static int launch_gemm8p(const me_gemm_args* a, hipStream_t st) {
     if (!g_ln_fused) b.ln_out = nullptr;
   }
   int rc;
-  if constexpr (BN == 256) {
+  const bool ups3_launch = a->gather == ME_GATHER_CONV3 && a->ups == 3;
+  if (ups3_launch) {   // its own instantiations: the term-free row pass, or the direct epilogues for everything else
+    if constexpr (GATHER && BN == 320) rc = epi == 0 ? launch_gemm8p_epi<BM, BN, true, 0, true>(b, st) : launch_gemm8p_epi<BM, BN, true, -1, true>(b, st);
+    else { me_set_error("me_gemm: internal: ups = 3 launch on a kernel without the mode"); return ME_EINVAL; }
+  } else if constexpr (BN == 256) {
     rc = epi == 0 ? launch_gemm8p_epi<BM, BN, GATHER, 0>(b, st) : launch_gemm8p_epi<BM, BN, GATHER, -1>(b, st);
   } else {
     switch (epi) {
@@ -1852,8 +1906,12 @@ static int gemm_dispatch(const me_gemm_args* a, void* stream) {
   if (((uintptr_t)a->X | (uintptr_t)a->W) & 15 || ((uintptr_t)a->C & 7)) { me_set_error("me_gemm: misaligned pointer"); return ME_EINVAL; }
   if (a->gather < 0 || a->gather > 2) { me_set_error("me_gemm: bad gather mode"); return ME_EINVAL; }
   if (a->gather == ME_GATHER_CONV3) {
-    if (a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0 || (a->stride != 1 && a->stride != 2) || a->ups < 0 || a->ups > 2 ||
+    if (a->Hin <= 0 || a->Win <= 0 || a->Hout <= 0 || a->Wout <= 0 || (a->stride != 1 && a->stride != 2) || a->ups < 0 || a->ups > 3 ||
         (a->pad0 != 0 && a->pad0 != 1) || a->M % (a->Hout * a->Wout)) { me_set_error("me_gemm: bad conv geometry"); return ME_EINVAL; }
+    if (a->ups == 3 && (a->stride != 1 || a->pad0 || a->Hout != 2 * a->Hin || a->Wout != 2 * a->Win || a->geglu)) {
+      me_set_error("me_gemm: ups = 3 (folded nearest 2x) needs stride 1, pad0 = 0, Hout = 2 Hin, Wout = 2 Win and weights [N, 16, K]");
+      return ME_EINVAL;
+    }
   }
   if (a->gather == ME_GATHER_TCONV) {
     const int ftot = a->frames_total > 0 ? a->frames_total : a->frames;
@@ -1875,10 +1933,23 @@ static int gemm_dispatch(const me_gemm_args* a, void* stream) {
     return ME_EINVAL;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // ups 3: the kernels work on one output parity at a time -- they get M (and sel_rows) in rows PER PARITY and four times the row tiles; every tile count
+  // below is multiplied back (pm), so that the launch lands where the ups = 1 launch of the same rows would.  No row sums from the epilogue (me_gemm appends the pass).
+  me_gemm_args par_args;
+  const int pm = a->gather == ME_GATHER_CONV3 && a->ups == 3 ? 4 : 1;
+  if (pm == 4) {
+    par_args = *a;
+    par_args.M = a->M / 4;
+    par_args.sel_rows = a->sel_rows / 4;
+    par_args.ln_out = nullptr;
+    a = &par_args;
+  }
+  // (ups 3 has its own instantiations of gemm_kernel, buffer- or global_load_lds-staged: ME_GEMM_STAGE=reg does not reach it)
+#define ME_LAUNCH_GEMM(BM_, BN_, STAGE_) (pm == 4 ? launch_gemm<BM_, BN_, STAGE_, 64, true>(a, st) : launch_gemm<BM_, BN_, STAGE_>(a, st))
   // N tile: every channel count of the model (320 ... 10240) is a multiple of 160 -> exact 128x160 tiles;
   // GEGLU needs whole (value, gate) 32-row pairs per wave -> 128; leftovers (4, 16, 32, 96, 256) -> 128 / 64 with a tail
   const bool wide = a->N % 128 == 0 || a->N % 64 != 0;
-  if (stage_impl() == STAGE_GLDS) {
+  if (stage_impl() == STAGE_GLDS || pm == 4) {
     // big tile when the grid still fills the chip: every model width is a multiple of 320
     // EVERY tile-count heuristic below uses Msel (round-4 advisor finding: only the big-tile and halo choices did, so the interior and boundary
     // pieces of a row-range TemporalConv could land on different kernel families than the unsplit launch).
@@ -1886,12 +1957,12 @@ static int gemm_dispatch(const me_gemm_args* a, void* stream) {
     // classifier-free-guidance prefix of the UNet graph -- and wants the rows it gets to be bitwise those of the full launch: the halo kernel and the
     // gather kernels add the (tap, channel slab) products in different orders)
     const int Msel = a->sel_rows > a->M ? a->sel_rows : a->M;
-    const long big_blocks = (long)((Msel + 255) / 256) * (a->N / 320);
+    const long big_blocks = (long)((Msel + 255) / 256) * pm * (a->N / 320);
     if (a->gather == ME_GATHER_CONV3 && a->stride == 1 && a->ups == 0 && !a->pad0 && a->N % 320 == 0 && a->K % 64 == 0 && a->Hin % 16 == 0 &&
         a->Win % 16 == 0 && !a->geglu && big_blocks >= halo_min_blocks() && conv_halo())
       return launch_conv_halo(a, st);
     const bool buf = a->K % 64 == 0 && buf_stage();   // scalar-offset buffer staging (no K tail, no packed-tap mode)
-    const int nit8 = (a->K / 64) * (a->gather == ME_GATHER_CONV3 ? 9 : (a->gather == ME_GATHER_TCONV ? 3 : 1));
+    const int nit8 = (a->K / 64) * (a->gather == ME_GATHER_CONV3 ? (pm == 4 ? 4 : 9) : (a->gather == ME_GATHER_TCONV ? 3 : 1));
     const bool dense = a->gather == ME_GATHER_DENSE;
     // GEGLU on the 256-wide 8-phase kernel from geglu_min_tiles() tiles of 256 x 256 on (round 6: its own threshold -- it used to share the 256 x 320 kernels')
     if (a->geglu && dense && buf && use_8p() > 0 && nit8 >= use_8p() && a->N % 256 == 0 && (long)((Msel + 255) / 256) * (a->N / 256) >= geglu_min_tiles())
@@ -1903,12 +1974,12 @@ static int gemm_dispatch(const me_gemm_args* a, void* stream) {
         if (!a->geglu) return dense ? launch_gemm8p<256, 320, false>(a, st) : launch_gemm8p<256, 320, true>(a, st);
         if (dense && a->N % 256 == 0 && (long)((Msel + 255) / 256) * (a->N / 256) >= big_min_blocks()) return launch_gemm8p<256, 256, false>(a, st);
       }
-      return buf ? launch_gemm<256, 320, STAGE_BUF>(a, st) : launch_gemm<256, 320, STAGE_GLDS>(a, st);
+      return buf ? ME_LAUNCH_GEMM(256, 320, STAGE_BUF) : ME_LAUNCH_GEMM(256, 320, STAGE_GLDS);
     }
     // grids of 256 < tiles < 512 (the M = 24576 level at N = 1280: 384 tiles = 1.5 rounds of the 256 CUs): 192-row tiles of the 8-phase kernel
     // make it 512 = 2 full rounds
     // (K >= 512 only: the K = 320 projections of this size are bound by their residual / output traffic and measured 7 % slower)
-    if (a->N % 320 == 0 && !a->geglu && buf && use_8p() > 0 && nit8 >= min_ktiles_192() && nit8 >= use_8p() && (long)((Msel + 191) / 192) * (a->N / 320) >= min_tiles_192())
+    if (a->N % 320 == 0 && !a->geglu && buf && use_8p() > 0 && nit8 >= min_ktiles_192() && nit8 >= use_8p() && (long)((Msel + 191) / 192) * pm * (a->N / 320) >= min_tiles_192())
       return dense ? launch_gemm8p<192, 320, false>(a, st) : launch_gemm8p<192, 320, true>(a, st);
     // ... and 128-row tiles of it (round 6) for DENSE grids from min_tiles_128() tiles of 128 x 320 on (the M = 6144 level at N = 1280: 192 tiles): +4 ... 30 % with
     // terms / row sums, +-0 without; the gather form measured 10 % SLOWER than 128 x 128 tiles there and stays out (profiles/r06_gemm_dispatch.txt)
@@ -1916,15 +1987,16 @@ static int gemm_dispatch(const me_gemm_args* a, void* stream) {
       return launch_gemm8p<128, 320, false>(a, st);
     // small grids (level 3 / mid block / ControlNet): 128-wide N tiles give 25 % more blocks until the 256 CUs have
     // two each (+8 % on those shapes; 64-row tiles measured worse)
-    const long blocks160 = (long)((Msel + 127) / 128) * ((a->N + 159) / 160);
+    const long blocks160 = (long)((Msel + 127) / 128) * pm * ((a->N + 159) / 160);
     {   // grids that leave more than half of the 256 CUs without a 128 x 128 tile (the M = 1536 level: 120 tiles): 64-wide tiles double the block count
-      const long blocks128 = (long)((Msel + 127) / 128) * ((a->N + 127) / 128);
-      if (a->N % 64 == 0 && blocks128 < n64_below()) return buf ? launch_gemm<128, 64, STAGE_BUF>(a, st) : launch_gemm<128, 64, STAGE_GLDS>(a, st);
+      const long blocks128 = (long)((Msel + 127) / 128) * pm * ((a->N + 127) / 128);
+      if (a->N % 64 == 0 && blocks128 < n64_below()) return buf ? ME_LAUNCH_GEMM(128, 64, STAGE_BUF) : ME_LAUNCH_GEMM(128, 64, STAGE_GLDS);
     }
-    if (a->N % 128 == 0 && blocks160 < 512) return buf ? launch_gemm<128, 128, STAGE_BUF>(a, st) : launch_gemm<128, 128, STAGE_GLDS>(a, st);
-    if (!a->geglu && a->N % 160 == 0 && tile160()) return buf ? launch_gemm<128, 160, STAGE_BUF>(a, st) : launch_gemm<128, 160, STAGE_GLDS>(a, st);
-    if (wide) return buf ? launch_gemm<128, 128, STAGE_BUF>(a, st) : launch_gemm<128, 128, STAGE_GLDS>(a, st);
-    return launch_gemm<128, 64, STAGE_GLDS>(a, st);
+    if (a->N % 128 == 0 && blocks160 < 512) return buf ? ME_LAUNCH_GEMM(128, 128, STAGE_BUF) : ME_LAUNCH_GEMM(128, 128, STAGE_GLDS);
+    if (!a->geglu && a->N % 160 == 0 && tile160()) return buf ? ME_LAUNCH_GEMM(128, 160, STAGE_BUF) : ME_LAUNCH_GEMM(128, 160, STAGE_GLDS);
+    if (wide) return buf ? ME_LAUNCH_GEMM(128, 128, STAGE_BUF) : ME_LAUNCH_GEMM(128, 128, STAGE_GLDS);
+    return ME_LAUNCH_GEMM(128, 64, STAGE_GLDS);
   }
+#undef ME_LAUNCH_GEMM
   return wide ? launch_gemm<128, 128, STAGE_REG>(a, st) : launch_gemm<128, 64, STAGE_REG>(a, st);
 }

@@ -103,12 +103,26 @@ class TemporalCall:
 # ---------------------------------------------------------------------------------------------
 def conv3x3(P: Packed, name: str, x: Act, stride: int = 1, ups: int = 0, **epi) -> Act:
     """InflatedConv3d 3x3 pad 1 (resnet_2d.py:28-36); stride-2 = Downsample2D (:94-125); ups=1 folds
-    Upsample2D's nearest-2x (:77) into the gather."""
+    Upsample2D's nearest-2x (:77) into the gather (ups_fold_on(): as four 2x2-tap convolutions, ops.gemm conv=(..., 3))."""
     hv, wv = x.h << ups, x.w << ups
     ho, wo = (hv - 1) // stride + 1, (wv - 1) // stride + 1
-    out = ops.gemm(x.t, P.mat(name + ".weight"), M=x.B * x.f * ho * wo, bias=P.vec(name + ".bias"),
-                   conv=(x.h, x.w, ho, wo, stride, ups), **epi)
+    w = None
+    if ups == 1 and stride == 1 and ups_fold_on():
+        # the nine taps of an output pixel touch four distinct input pixels: four 2x2-tap convolutions over the low-res grid, one per output
+        # parity, on pre-summed weights (me_gemm gather mode ups = 3) -- 4/9 of the products.  None: a trainer owns the weight (Packed.mat_ups).
+        w = P.mat_ups(name + ".weight")
+    if w is not None:
+        ups = 3
+    else:
+        w = P.mat(name + ".weight")
+    out = ops.gemm(x.t, w, M=x.B * x.f * ho * wo, bias=P.vec(name + ".bias"), conv=(x.h, x.w, ho, wo, stride, ups), **epi)
     return x.like(out, ho, wo)
+
+
+def ups_fold_on() -> bool:
+    """The folded form of the upsampler convolutions: when the backend has it (the CPU emulation does not), outside a differentiated run (gemm_dx
+    differentiates ups = 1) and unless ME_UPS_FOLD=0 (A/B switch, read per call)."""
+    return not getattr(ops, "recording", False) and getattr(ops, "UPS_FOLD", False) and __import__("os").environ.get("ME_UPS_FOLD", "1") != "0"
 
 
 def resnet_block(P: Packed, p: str, x: Act, temb: torch.Tensor, temb_off: int, *, per_frame_stats: bool, eps: float = 1e-5, shard=None,

@@ -75,6 +75,7 @@ def empty(rows: int, cols: int, like: torch.Tensor) -> torch.Tensor:
 ATTN_ITEM_ORDER = os.environ.get("ME_ATTN_ITEM_ORDER", "1") != "0"   # the edited launches walk their items (recon g, edit g, recon g + 1, ...): me_attn_args.item_order
 ROW_RANGE = True       # this backend implements gemm(row_range=...) (me_gemm_args.m_off)
 LN_FOLD = True         # ... and gemm(ln=..., ln_out=...) / ln_stats (ABI 9: LayerNorm folded into the projection that consumes it)
+UPS_FOLD = True        # ... and gemm(conv=(..., ups = 3)): a 3x3 convolution over a nearest-2x upsample as four 2x2-tap convolutions (weights.Packed.mat_ups)
 HEAD_MAJOR_KV = True   # this backend implements gemm(head_major=...) / 3-D k, v in attention (the CPU emulation and the autodiff recorder do not)
 
 
@@ -86,7 +87,7 @@ def gemm(x: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, out: Opti
          row_range: Optional[Tuple[int, int]] = None, ln: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, float]] = None, ln_out: bool = False):
     """out[m, n] = epilogue(sum_{tap,c} x[src(m,tap), c] * w[n, tap, c]).
 
-    w: fp16 [N, taps, K] (taps = 1 dense, 9 for ``conv=(Hin, Win, Hout, Wout, stride, ups)``,
+    w: fp16 [N, taps, K] (taps = 1 dense, 9 for ``conv=(Hin, Win, Hout, Wout, stride, ups)`` -- 16 at ups = 3, the folded form of ups = 1 --,
     3 for ``tconv=(frames, npix, chunk)``).  res_rows / res2_rows > 0: res / res2 holds that many rows, output row m reads row m % rows.
     row_range = (lo, hi): only the output rows [lo, hi) of the M-row problem are computed (into `out`, which must be given and hold all M rows): the
     interior / boundary launches of a frame-sharded TemporalConv (me_gemm_args.m_off).
@@ -105,8 +106,8 @@ def gemm(x: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, out: Opti
         a.gather = capi.GATHER_CONV3
         a.Hin, a.Win, a.Hout, a.Wout, a.stride, a.ups = conv[:6]
         a.pad0 = conv[6] if len(conv) > 6 else 0     # 1: pad (0,1,0,1) instead of 1 all round (VAE encoder downsampling)
-        if taps != 9:
-            raise ValueError("gemm: conv needs 9 taps")
+        if taps != (16 if a.ups == 3 else 9):
+            raise ValueError("gemm: conv needs 9 taps (16 folded ones at ups = 3)")
     elif tconv is not None:
         a.gather = capi.GATHER_TCONV
         a.frames, a.npix, a.chunk = tconv[:3]
@@ -190,8 +191,13 @@ def gemm(x: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, out: Opti
         rows_in = (M // (conv[2] * conv[3])) * conv[0] * conv[1] if conv is not None else M
         n_terms = (res is not None) + (res2 is not None)
         n_hm = panels.numel() // M if panels is not None else 0      # output columns that leave as head-major panels (counted like any other output byte)
-        _pe(e0, "gemm", 2.0 * M * N * K * taps, 2.0 * (rows_in * K + N * K * taps + M * n_out * (1 + n_terms) + M * n_hm), f"M{M} N{N} K{K} taps{taps}{' geglu' if geglu else ''}{' +b' if bias is not None else ''}{' +rv' if rowvec is not None else ''}"
-            f"{' +res' if res is not None else ''}{' +res2' if res2 is not None else ''}{' act' + str(act) if act else ''}{' a' + str(alpha) if alpha != 1.0 else ''}{' ln' if ln is not None else ''}{' lnout' if ln_out else ''}", _last_kernel())
+        # (bytes, like flops, are the reference-semantics figure: the nine-tap weight read once.  The folded launch reads its 16 stored taps once, 16 / 9 of that --
+        #  1.5 % of the L1->L0 launch's algorithmic bytes; there is no "executed bytes" column to put it in.)
+        ref_taps, exec_flops = taps, None
+        if taps == 16:      # folded nearest-2x convolution: the reference executes nine taps per output pixel, the kernel four
+            ref_taps, exec_flops = 9, 2.0 * M * N * K * 4
+        _pe(e0, "gemm", 2.0 * M * N * K * ref_taps, 2.0 * (rows_in * K + N * K * ref_taps + M * n_out * (1 + n_terms) + M * n_hm), f"M{M} N{N} K{K} taps{taps}{' geglu' if geglu else ''}{' +b' if bias is not None else ''}{' +rv' if rowvec is not None else ''}"
+            f"{' +res' if res is not None else ''}{' +res2' if res2 is not None else ''}{' act' + str(act) if act else ''}{' a' + str(alpha) if alpha != 1.0 else ''}{' ln' if ln is not None else ''}{' lnout' if ln_out else ''}", _last_kernel(), exec_flops)
     if panels is not None and n_out == 0:
         return None, panels
     out = out[:M, :n_out] if (out.shape[0] != M or out.shape[1] != n_out) else out

@@ -6,6 +6,7 @@ fp16 tensors in the layouts the kernels consume.
   Conv2d  [Co, Ci, 1, 1]    -> [Co, 1, Ci]
   Conv1d  [Co, Ci, k]       -> [Co, k, Ci]   (TemporalConv, k in {1, 3})
   GEGLU   [8C, C] (+bias)   -> rows interleaved in blocks of 16 value rows / 16 gate rows
+  Conv2d  [Co, Ci, 3, 3] behind a nearest-2x upsample -> also [Co, 16, Ci] (mat_ups: four 2x2-tap convolutions, taps pre-summed)
   q|k|v (or k|v)            -> one fused [3C, 1, K] projection
   all ResnetBlock2D.time_emb_proj -> one [sum(Cout), 1, 1280] projection
 
@@ -49,6 +50,7 @@ class Packed:
         self.prefix = prefix
         self.cache: Dict[str, torch.Tensor] = {}
         self.live: Dict[str, Callable[[], torch.Tensor]] = {}   # reference name -> its current value while a trainer owns it (fp32 master, reference layout)
+        self._rehomed: set = set()   # cache keys moved into a caller-owned bucket (rehome): their owner rewrites them in place
 
     def make_private(self) -> None:
         """Give this store its own (mutable) name -> tensor mapping before the first parameter is replaced: the caller's state dict -- often
@@ -121,6 +123,35 @@ class Packed:
 
     def mat(self, name: str) -> torch.Tensor:
         return self._get("mat:" + name)
+
+    @staticmethod
+    def fold_ups(w: torch.Tensor) -> torch.Tensor:
+        """[N, Cin, 3, 3] -> [N, 16, Cin], unrounded: a 3x3 convolution over a nearest-2x upsample as four 2x2-tap convolutions over the
+        low-resolution grid.  Middle index 4 (2 py + px) + 2 ty + tx: tap (ty, tx) of output parity (py, px) reads low-res pixel
+        (y + py - 1 + ty, x + px - 1 + tx) and holds the sum of the 3x3 taps (ky, kx) whose virtual pixel (2y + py - 1 + ky, 2x + px - 1 + kx)
+        lies inside it -- rows: ky -> ty = (py + ky + 1) // 2 - py, columns alike."""
+        n, cin = w.shape[:2]
+        out = torch.zeros((n, 2, 2, 2, 2, cin), dtype=w.dtype)      # [n, py, px, ty, tx, c]
+        for py in range(2):
+            for px in range(2):
+                for ky in range(3):
+                    for kx in range(3):
+                        out[:, py, px, (py + ky + 1) // 2 - py, (px + kx + 1) // 2 - px] += w[:, :, ky, kx]
+        return out.reshape(n, 16, cin)
+
+    def mat_ups(self, name: str) -> Optional[torch.Tensor]:
+        """The folded [N, 16, K] weight of the convolution behind a nearest-2x upsample (me_gemm gather mode ups = 3): the taps summed in fp32,
+        rounded to the store's dtype ONCE; packed once under its own key (`update` drops it with every other tensor built from `name`).
+        None -- the caller keeps the 9-tap form -- while a trainer rewrites this parameter's packed tensor in place (`live`, `rehome`): the in-place
+        refresh knows the plain packings and the LayerNorm folds only, a folded copy would go stale behind it."""
+        # (only the plain `mat:` packing of a convolution is ever rehomed -- AdapterTrainer rehomes adapter_pack's keys, and a 3x3 weight has no other
+        #  packing -- so the exact key is the whole test; a new packing kind of convolution weights would have to be named here)
+        if name in self.live or ("mat:" + name) in self._rehomed:
+            self.cache.pop("ups4:" + name, None)
+            return None
+        key = "ups4:" + name
+        hit = self.cache.get(key)
+        return hit if hit is not None else self._put(key, self.fold_ups(self.raw(name)))
 
     def mat32(self, name: str) -> torch.Tensor:
         """fp32 [N, taps, K] (conv_small reads its tiny weights through the scalar cache)."""
@@ -242,6 +273,7 @@ class Packed:
         storage.copy_(t.reshape(-1))
         v = storage.view(t.shape)
         self.cache[key] = v
+        self._rehomed.add(key)      # (its owner rewrites it in place: no derived copy of it may be cached, mat_ups)
         return v
 
     def unpack_grad(self, key: str, g: torch.Tensor) -> Dict[str, torch.Tensor]:

@@ -46,6 +46,9 @@ def bench_gemm():
              ("L2 conv 2560->1280", B * f * 256, 1280, 2560, (16, 16, 16, 16, 1, 0), None, False),
              ("L1->L0 ups conv 640", B * f * 4096, 640, 640, (32, 32, 64, 64, 1, 1), None, False),
              ("L2->L1 ups conv 1280", B * f * 1024, 1280, 1280, (16, 16, 32, 32, 1, 1), None, False),
+             ("L1->L0 ups conv 640 folded", B * f * 4096, 640, 640, (32, 32, 64, 64, 1, 3), None, False),
+             ("L2->L1 ups conv 1280 folded", B * f * 1024, 1280, 1280, (16, 16, 32, 32, 1, 3), None, False),
+             ("L3->L2 ups conv 1280 folded", B * f * 256, 1280, 1280, (8, 8, 16, 16, 1, 3), None, False),
              ("cn L0 conv3x3", 2 * f * 4096, 320, 320, (64, 64, 64, 64, 1, 0), None, False),
              ("L0 conv_out 320->4", B * f * 4096, 4, 320, (64, 64, 64, 64, 1, 0), None, False),
              ("cond 16->16 @512", 48 * 512 * 512, 16, 16, (512, 512, 512, 512, 1, 0), None, False),
@@ -55,7 +58,7 @@ def bench_gemm():
     for name, M, N, K, conv, tconv, geglu in rows:
         taps = 9 if conv else (3 if tconv else 1)
         rows_in = M if not conv else (M // (conv[2] * conv[3])) * conv[0] * conv[1]
-        x, w = rnd(rows_in, K), rnd(N, taps, K)
+        x, w = rnd(rows_in, K), rnd(N, 16 if conv and conv[5] == 3 else taps, K)      # (folded rows: 16 stored taps, TF/s at the nine reference taps)
         ms = timeit(lambda: ops.gemm(x, w, M=M, conv=conv, tconv=tconv, geglu=geglu))
         tot += ms
         print(f"{name:24s} {M:8d} {N:6d} {K*taps:6d} {ms:8.3f} {2.0*M*N*K*taps/ms/1e9:7.1f}")
@@ -88,6 +91,44 @@ def bench_lnfold():
         t_k = timeit(lambda: ops.ln_stats(x))
         print(f"L{li} out + res: plain {t_p:.3f} ms, with row sums {t_s:.3f} ms (+{(t_s / t_p - 1) * 100:.1f} %); me_ln_stats alone {t_k:.3f} ms")
         del x, w, res
+
+
+def bench_upsfold():
+    """The upsampler convolutions as ups = 1 (nine taps through the nearest-2x gather) against ups = 3 (four 2x2-tap convolutions on pre-summed weights,
+    weights.Packed.fold_ups): same process, same data, ALTERNATING, REPS medians-of-one each; prints every repeat's time, the spread and the ratio, and
+    the rel-L2 between the two outputs.  The three UNet shapes, then the VAE decoder's (one 512 x 512 image per frame, 8 frames)."""
+    from motioneditor_amd.weights import Packed
+    B, f = 4, 24
+    cases = [("L1->L0 ups conv 640", B * f, 640, 32), ("L2->L1 ups conv 1280", B * f, 1280, 16), ("L3->L2 ups conv 1280", B * f, 1280, 8),
+             ("vae 64->128 ups conv 512", 8, 512, 64), ("vae 128->256 ups conv 512", 8, 512, 128), ("vae 256->512 ups conv 256", 8, 256, 256)]
+    reps = 7
+    print(f"{'ups fold':28s} {'M':>8s} {'N':>5s} {'ups1 ms':>8s} {'spread':>7s} {'TF/s':>7s} {'ups3 ms':>8s} {'spread':>7s} {'TF/s 9tap':>9s} {'x':>5s} {'rel-L2':>9s}  kernels", flush=True)
+    for name, n_img, C, hw in cases:
+        M = n_img * 4 * hw * hw
+        x = rnd(n_img * hw * hw, C)
+        w4 = torch.randn(C, C, 3, 3) * (9 * C) ** -0.5
+        w9, w16 = Packed._as_taps(w4).contiguous().half().to(dev), Packed.fold_ups(w4).half().contiguous().to(dev)
+        bias = rnd(C)
+        runs = {1: lambda: ops.gemm(x, w9, M=M, bias=bias, conv=(hw, hw, 2 * hw, 2 * hw, 1, 1)), 3: lambda: ops.gemm(x, w16, M=M, bias=bias, conv=(hw, hw, 2 * hw, 2 * hw, 1, 3))}
+        outs, kern, ts = {}, {}, {1: [], 3: []}
+        for u in (1, 3):
+            outs[u] = runs[u]()
+            kern[u] = ops._last_kernel()
+            runs[u]()
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for u in (1, 3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); runs[u](); e1.record()
+                torch.cuda.synchronize()
+                ts[u].append(e0.elapsed_time(e1))
+        med = {u: sorted(ts[u])[reps // 2] for u in ts}
+        spread = {u: max(ts[u]) - min(ts[u]) for u in ts}
+        fl = 2.0 * M * C * C * 9
+        rel = float((outs[3].float() - outs[1].float()).norm() / outs[1].float().norm())
+        print(f"{name:28s} {M:8d} {C:5d} {med[1]:8.3f} {spread[1]:7.3f} {fl / med[1] / 1e9:7.1f} {med[3]:8.3f} {spread[3]:7.3f} {fl / med[3] / 1e9:9.1f} {med[1] / med[3]:5.2f} {rel:9.2e}  {kern[1]} | {kern[3]}", flush=True)
+        print(f"    ups1 repeats {' '.join(f'{t:.3f}' for t in ts[1])}   ups3 repeats {' '.join(f'{t:.3f}' for t in ts[3])}", flush=True)
+        del x, w9, w16, outs
 
 
 def bench_gemm_8p():
@@ -508,6 +549,8 @@ if __name__ == "__main__":
         bench_gemm_8p()
     if "gemmabl" in what:
         bench_gemm_abl()
+    if "upsfold" in what:
+        bench_upsfold()
     if "rowepi" in what:
         bench_gemm_rowepi()
     if "tileorder" in what:

@@ -19,6 +19,9 @@ the checkpoint directory, or seeded synthetic weights and a byte-level vocabular
 reads the clip with data.dataset.VideoDataset (images/, man.mask/, source_condition/openposefull/, target_condition/openposefull/; --frames and --size are
 its n_sample_frames and width / height) and saves the edit and the reconstruction as sample/{target prompt}.gif and sample/{target prompt}-inv.gif under
 --out (inference.py:328-329).
+    python examples/run_edit.py --prompt "a girl is dancing" --target-prompt "a boy is dancing" --target-prompt "a robot is dancing" --out outputs/case-1
+edits the clip towards every --target-prompt (up to 3) in ONE call -- the reference loops over its prompts, one whole run each (inference.py:298-323); here
+the reconstruction branch is computed once per step and shared -- and saves sample/{target}.gif per target plus one -inv.gif.
 """
 from __future__ import annotations
 
@@ -77,18 +80,32 @@ def clip_inputs(a, device: str = "cuda") -> dict:
     return x
 
 
-def save_samples(out_dir: str, target_prompt: str, sample_inv, sample_gen) -> list:
-    """inference.py:328-329."""
+def save_samples(out_dir: str, target_prompt, sample_inv, sample_gen) -> list:
+    """inference.py:328-329.  target_prompt: a string, or the list of target prompts of a several-target run (sample_gen then holds one edit per
+    target): sample/{target}.gif for each, and the one reconstruction as sample/{first target}-inv.gif."""
     from motioneditor_amd import util
-    paths = [f"{out_dir}/sample/{target_prompt}.gif", f"{out_dir}/sample/{target_prompt}-inv.gif"]
-    util.save_videos_grid(sample_gen, paths[0])
-    util.save_videos_grid(sample_inv, paths[1])
+    targets = [target_prompt] if isinstance(target_prompt, str) else list(target_prompt)
+    if len(targets) != sample_gen.shape[0]:
+        raise ValueError(f"{len(targets)} target prompts for {sample_gen.shape[0]} edits")
+    paths = [f"{out_dir}/sample/{t}.gif" for t in targets] + [f"{out_dir}/sample/{targets[0]}-inv.gif"]
+    for k, path in enumerate(paths[:-1]):
+        util.save_videos_grid(sample_gen[k:k + 1], path)
+    util.save_videos_grid(sample_inv, paths[-1])
     return paths
 
 
-def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, output_type: str = "tensor", graphed: bool = False, prompts=None):
+def extra_target_embeddings(n: int, seed: int = 33) -> torch.Tensor:
+    """Synthetic stand-ins for CLIP(target prompt 2 .. n) beside harness_inputs' pinned (source, target 1) pair."""
+    from motioneditor_amd import synth
+    return torch.from_numpy(synth.synth_normal("harness.cond.more", (n - 1, 77, 768), seed, 0.3))
+
+
+def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, output_type: str = "tensor", graphed: bool = False, prompts=None, n_targets: int = 1):
     """inference.py:259-326 for one (source prompt, target prompt) pair.  Returns (sample_inv, sample_gen, ddim_inv_latent).
-    prompts = [source, target]: the pipeline's own text encoder and tokenizer encode them (and the empty prompt) instead of the tensors in `x`."""
+    prompts = [source, target]: the pipeline's own text encoder and tokenizer encode them (and the empty prompt) instead of the tensors in `x`.
+    prompts = [source, target_1 .. target_N] (or n_targets = N with the synthetic embeddings): every target in the one call, all towards the clip's one target
+    skeleton as the reference's loop over its prompts does (:298-302); sample_gen then holds the N edits."""
+    n_targets = len(prompts) - 1 if prompts else n_targets
     from motioneditor_amd import util
     from motioneditor_amd.attn_control import (FullySelfAttentionControlMask, TemporalSelfAttentionControl,
                                                regiter_fully_attention_editor_diffusers, regiter_temporal_attention_editor_diffusers)
@@ -101,7 +118,7 @@ def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, out
     inv_sched.set_timesteps(inv_steps)
     ddim_inv_latent = util.ddim_inversion(pipe, inv_sched, latents, inv_steps, prompt="", normal_infer=True,
                                           text_embeddings=None if prompts else x["negative_text_embeddings"])[-1]   # (:288-293; prompt "" = the empty-prompt embedding)
-    ddim_inv_latent = ddim_inv_latent.repeat(2, 1, 1, 1, 1)                                                # (:296)
+    ddim_inv_latent = ddim_inv_latent.repeat(1 + n_targets, 1, 1, 1, 1)                                    # (:296)
     tgt = x["target_skeleton"]
     skeleton = torch.cat([torch.zeros_like(tgt), tgt, torch.zeros_like(tgt), tgt], dim=0)                  # (:300-302)
     ted = TemporalSelfAttentionControl(start_step=4, start_layer=10)
@@ -109,11 +126,13 @@ def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, out
     sed = FullySelfAttentionControlMask(start_step=4, start_layer=10, source_masks=x["source_masks"], target_masks=None, rectangle_source_masks=None)
     regiter_fully_attention_editor_diffusers(pipe, sed)
     emb = {} if prompts else dict(text_embeddings=x["text_embeddings"], negative_text_embeddings=x["negative_text_embeddings"])
-    sample = pipe(list(prompts) if prompts else ["a source prompt", "a target prompt"], video_length=f, height=H, width=W, num_inference_steps=steps,
+    if not prompts and n_targets > 1:
+        emb["text_embeddings"] = torch.cat([x["text_embeddings"], extra_target_embeddings(n_targets).to(x["text_embeddings"].device)])
+    sample = pipe(list(prompts) if prompts else ["a source prompt"] + ["a target prompt"] * n_targets, video_length=f, height=H, width=W, num_inference_steps=steps,
                   guidance_scale=guidance, latents=ddim_inv_latent, uncond_embeddings=None, skeleton=skeleton, source_masks=None, target_masks=None,
                   rectangle_source_masks=None, background_latents=None, output_type=output_type, **emb).images
-    assert sample.shape[0] == 2
-    sample_inv, sample_gen = sample.chunk(2)
+    assert sample.shape[0] == 1 + n_targets
+    sample_inv, sample_gen = sample[:1], sample[1:]
     return sample_inv, sample_gen, ddim_inv_latent
 
 
@@ -145,7 +164,8 @@ def parser() -> argparse.ArgumentParser:
                     help="who issues the ~1100 launches of a denoising step: 'plan' = one me_denoise_step call per step (the launch list is recorded at the first step of "
                          "each editor gating, csrc/plan.hip), 'eager' = Python, launch by launch; the results are bitwise the same")
     ap.add_argument("--prompt", default=None, help="source prompt: encode the prompts with the native CLIP text encoder instead of feeding synthetic embeddings")
-    ap.add_argument("--target-prompt", default=None, help="target prompt (default: the source prompt)")
+    ap.add_argument("--target-prompt", action="append", default=None,
+                    help="target prompt (default: the source prompt); give it several times (up to 3) to edit the clip towards every one of them in one call")
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
     add_clip_arguments(ap)
     ap.add_argument("--out", default=None, help="directory that receives sample/{target prompt}.gif (the edit) and sample/{target prompt}-inv.gif (the reconstruction)")
@@ -159,16 +179,19 @@ def main():
     prompts = None
     if a.prompt is not None:
         pipe.text_encoder, pipe.tokenizer = text_models(a.checkpoint)
-        prompts = [a.prompt, a.target_prompt if a.target_prompt is not None else a.prompt]
+        prompts = [a.prompt] + (a.target_prompt if a.target_prompt else [a.prompt])
     x = clip_inputs(a) if a.video_dir else {k: v.cuda() for k, v in harness_inputs(a.frames, a.size, a.size).items()}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps, prompts=prompts)
+    inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps, prompts=prompts, n_targets=len(a.target_prompt or [None]))
     torch.cuda.synchronize()
     print(f"{a.frames} frames {a.size}x{a.size}: encode + {a.inv_steps} inversion steps + {a.steps} denoising steps + decode in {time.perf_counter() - t0:.2f} s; "
           f"reconstruction {tuple(inv.shape)}, edit {tuple(gen.shape)}, range [{float(gen.min()):.3f}, {float(gen.max()):.3f}]")
     if a.out:
-        print("saved", *save_samples(a.out, prompts[1] if prompts else "a target prompt", inv, gen))
+        names = prompts[1:] if prompts else (a.target_prompt or ["a target prompt"])
+        if len(set(names)) != len(names):     # the same target twice: keep the files apart
+            names = [f"{t} ({k + 1})" for k, t in enumerate(names)]
+        print("saved", *save_samples(a.out, names, inv, gen))
 
 
 if __name__ == "__main__":

@@ -75,9 +75,12 @@ class FullySelfAttentionControlMask(MutualSelfAttentionControl):
                 attention_mask=None, call=None, text_seg=None, **kwargs):
         if is_cross or self.cur_step not in self.step_idx or self.cur_att_layer // 2 not in self.layer_idx:  # reference :434
             return super().forward(is_cross=is_cross, place_in_unet=place_in_unet, num_heads=num_heads, call=call, text_seg=text_seg)
-        if call.B not in (2, 4):
-            raise ValueError("edited attention expects batch 4 = [uncond.rec, uncond.edit, cond.rec, cond.edit] (reference :439-441) "
-                             "or one (rec, edit) pair on a CFG-parallel rank")
+        br = getattr(call, "branches", None)     # which rows are edits, and of which source (segments.Branches); None: (rec, edit) pairs
+        if br is None and call.B not in (2, 4):
+            raise ValueError("edited attention expects batch 4 = [uncond.rec, uncond.edit, cond.rec, cond.edit] (reference :439-441), "
+                             "one (rec, edit) pair on a CFG-parallel rank, or a branch description of the batch (segments.Branches)")
+        if br is not None and br.B != call.B:
+            raise ValueError(f"edited attention: the branch description covers {br.B} rows, the batch has {call.B}")
         if (num_heads * call.f) % 8:
             raise ValueError("heads * frames must be divisible by 8 (reference :377)")
-        return call.run(*segments.edited_spatial(call.f, call.q.device, self.binary_masks, call.B, getattr(call, "shard", None)), mask=self.mask_planes(call.N, call.q.device))
+        return call.run(*segments.edited_spatial(call.f, call.q.device, self.binary_masks, call.B, getattr(call, "shard", None), br), mask=self.mask_planes(call.N, call.q.device))

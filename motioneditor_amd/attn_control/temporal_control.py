@@ -1,8 +1,10 @@
 """TemporalSelfAttentionControl (reference ``motion_editor/attn_control/temporal_control.py:26-89``):
 on edited layers/steps the edit-branch queries attend the reconstruction branch's K/V (full
-replacement), causal mask kept.  In the fused kernel that is just a batch remap kv_map=[0,0,2,2]."""
+replacement), causal mask kept.  In the fused kernel that is just a batch remap: kv_map = the source row of every batch row,
+[0,0,2,2] for (rec, edit) pairs, [0,0,0,3,3,3] for two targets per classifier-free-guidance half (segments.Branches)."""
 from __future__ import annotations
 
+from .. import segments
 from .temporal_control_utils import TemporalAttentionBase
 
 
@@ -22,6 +24,13 @@ class TemporalSelfAttentionControl(TemporalAttentionBase):
                 attention_mask=None, call=None, **kwargs):
         if is_cross or self.cur_step not in self.step_idx or self.cur_att_layer not in self.layer_idx:  # reference :74
             return super().forward(is_cross=is_cross, place_in_unet=place_in_unet, num_heads=num_heads, call=call)
-        if call.B not in (2, 4):
-            raise ValueError("edited temporal attention expects batch 4 (reference :77-85) or one (rec, edit) pair")
-        return call.run(kv_map=[0, 0, 2, 2][:call.B])
+        br = getattr(call, "branches", None)
+        if br is None:
+            if call.B not in (2, 4):
+                raise ValueError("edited temporal attention expects batch 4 (reference :77-85), one (rec, edit) pair, or a branch description of the batch")
+            br = segments.Branches.pairs(call.B)
+        if br.B != call.B:
+            raise ValueError(f"edited temporal attention: the branch description covers {br.B} rows, the batch has {call.B}")
+        if call.B > segments.TATTN_MAX_BATCH:
+            raise ValueError(f"edited temporal attention: one launch holds {segments.TATTN_MAX_BATCH} batch rows (me_tattn_args.kv_map), got {call.B}")
+        return call.run(kv_map=list(br.src))

@@ -69,6 +69,7 @@ class AttnCall:
     is_cross: bool
     shard: object = None   # parallel.FrameShard: k/v are then the all-gather of every rank's frames (part-major items)
     q_items: int = 0       # > 0: q holds that many query items; item i reads item i % q_items (queries shared by the CFG halves, unet_forward)
+    branches: object = None   # segments.Branches of these B rows (which are edits, and of which source); None: the editors assume (rec, edit) pairs
 
     def run(self, seg_item: torch.Tensor, seg_mode: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         return ops.attention(self.q, self.k, self.v, heads=HEADS, dh=self.dh, n_items=self.B * self.f, nq=self.N, nk=self.nk,
@@ -86,6 +87,7 @@ class TemporalCall:
     dh: int
     shard: object = None   # parallel.FrameShard: q holds the local frames, k/v all frames (all-gathered, part-major)
     parts: int = 0         # > 1: after the frame<->pixel all-to-all -- q, k, v hold ALL f frames of N pixels, part-major
+    branches: object = None   # segments.Branches of these B rows; None: the temporal editor assumes (rec, edit) pairs
 
     def run(self, kv_map: Optional[Sequence[int]] = None) -> torch.Tensor:
         if self.parts > 1:
@@ -238,7 +240,7 @@ def _qkv(P: Packed, p: str, n: "LN", C: int, shard, B: int = 0, N: int = 0, head
     return q, kv[:, :C], kv[:, C:]
 
 
-def _temporal_attn(P: Packed, p: str, n: "LN", C: int, B: int, f: int, N: int, dh: int, shard, editor=None, place: str = "") -> torch.Tensor:
+def _temporal_attn(P: Packed, p: str, n: "LN", C: int, B: int, f: int, N: int, dh: int, shard, editor=None, place: str = "", branches=None) -> torch.Tensor:
     """Causal attention over frames of the projections of `n` (the normed stream, rows (b, local frame, pixel)); returns the
     attention output in the same row order.  Frame-sharded: the rows of `n` go through the frame<->pixel all-to-all BEFORE
     the q|k|v projection (a row-wise GEMM commutes with the row exchange, so C columns travel instead of 3C), every rank
@@ -249,10 +251,10 @@ def _temporal_attn(P: Packed, p: str, n: "LN", C: int, B: int, f: int, N: int, d
     if shard is not None and shard.pixel_sharded(N):
         r = shard.to_pixel_shards(n.rows(), B * f, N, ops.copy_blocks)     # (the NORMALISED rows travel: the exchange needs a tensor of its own anyway)
         qkv = ops.gemm(r, P.fused([p + ".to_q.weight", p + ".to_k.weight", p + ".to_v.weight"]))
-        a = go(TemporalCall(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, shard.f_total, N // shard.world, dh, None, shard.world))
+        a = go(TemporalCall(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, shard.f_total, N // shard.world, dh, None, shard.world, branches))
         return shard.to_frame_shards(a, B * f, N, ops.copy_blocks)
     q, k, v = _qkv(P, p, n, C, shard)
-    return go(TemporalCall(q, k, v, B, f, N, dh, shard))
+    return go(TemporalCall(q, k, v, B, f, N, dh, shard, 0, branches))
 
 
 def _tconv(P: Packed, name: str, h_ext: torch.Tensor, x: "Act", chunk: int, shard, **epi) -> torch.Tensor:
@@ -291,7 +293,8 @@ def _ext_rows(x: "Act", shard) -> int:
 
 
 def basic_block(P: Packed, p: str, x: Act, text: Optional[torch.Tensor], text_seg, *, spatial, temporal, place: str,
-                sc_attn: bool, has_temp: bool, shard=None, text_kv: Optional[torch.Tensor] = None, expand: int = 1, stats: Optional[torch.Tensor] = None) -> Act:
+                sc_attn: bool, has_temp: bool, shard=None, text_kv: Optional[torch.Tensor] = None, expand: int = 1, stats: Optional[torch.Tensor] = None,
+                branches=None) -> Act:
     """BasicTransformerBlock.forward (attention_2d.py:493-547) on rows [(B f N), C].
     expand > 1 (unet_forward's CFG prefix): x holds B / expand distinct batch entries -- entry b + k B / expand of the full batch would be a
     bit-for-bit copy of entry b up to the text cross-attention -- so attn1 runs once per distinct entry, attn2 reads the shared queries
@@ -304,7 +307,8 @@ def basic_block(P: Packed, p: str, x: Act, text: Optional[torch.Tensor], text_se
     # plain per-frame self-attention (ControlNet, normal_infer) needs no other frames; [prev | cur] needs ONE halo frame
     sh1 = shard.prev_frame_view() if (shard is not None and sc_attn) else None
     q, k, v = _qkv(P, p + ".attn1", LN(P, p + ".norm1", t, stats), C, sh1, x.B, x.N, head_major=True)
-    call = AttnCall(q, k, v, x.B, x.f, x.N, dh, x.N, False, sh1)
+    # (branches describes the FULL batch: the shared CFG prefix, expand > 1, holds half of it and is never edited)
+    call = AttnCall(q, k, v, x.B, x.f, x.N, dh, x.N, False, sh1, 0, branches if expand == 1 else None)
     if spatial is not None:
         a = spatial(call=call, is_cross=False, place_in_unet=place, num_heads=HEADS)
     elif sc_attn:
@@ -337,19 +341,19 @@ def basic_block(P: Packed, p: str, x: Act, text: Optional[torch.Tensor], text_se
     t, st = feed_forward(P, p + ".ff", LN(P, p + ".norm3", t, st), t, want_stats=has_temp)
     # --- temporal attention over frames, causal (attention_2d.py:534-545)
     if has_temp:
-        a = _temporal_attn(P, p + ".attn_temp", LN(P, p + ".norm_temp", t, st), C, x.B, x.f, x.N, dh, shard, temporal, place)
+        a = _temporal_attn(P, p + ".attn_temp", LN(P, p + ".norm_temp", t, st), C, x.B, x.f, x.N, dh, shard, temporal, place, branches)
         t = ops.gemm(a, P.mat(p + ".attn_temp.to_out.0.weight"), bias=P.vec(p + ".attn_temp.to_out.0.bias"), res=t)
     return x.like(t)
 
 
 def transformer2d(P: Packed, p: str, x: Act, text, text_seg, *, spatial=None, temporal=None, place: str = "", sc_attn: bool = True,
-                  has_temp: bool = True, shard=None, out: Optional[torch.Tensor] = None, text_kv: Optional[dict] = None, expand: int = 1) -> Act:
+                  has_temp: bool = True, shard=None, out: Optional[torch.Tensor] = None, text_kv: Optional[dict] = None, expand: int = 1, branches=None) -> Act:
     """Transformer2DModel.forward (attention_2d.py:338-389): per-frame GroupNorm(32, eps 1e-6), 1x1 proj in/out.
     out: where the block's result is written (a column slice of the next skip-concat buffer)."""
     n = ops.groupnorm(x.t, P.vec(p + ".norm.weight"), P.vec(p + ".norm.bias"), rows_per_group=x.N, eps=1e-6, silu=False)
     t, st = _gemm_st(n, P.mat(p + ".proj_in.weight"), bias=P.vec(p + ".proj_in.bias"))
     t = basic_block(P, p + ".transformer_blocks.0", x.like(t), text, text_seg, spatial=spatial, temporal=temporal, place=place,
-                    sc_attn=sc_attn, has_temp=has_temp, shard=shard, text_kv=None if text_kv is None else text_kv[p], expand=expand, stats=st).t
+                    sc_attn=sc_attn, has_temp=has_temp, shard=shard, text_kv=None if text_kv is None else text_kv[p], expand=expand, stats=st, branches=branches).t
     y = ops.gemm(t, P.mat(p + ".proj_out.weight"), bias=P.vec(p + ".proj_out.bias"), res=x.t, **({} if out is None else {"out": out}),
                  **({"res_rows": x.t.shape[0]} if expand > 1 else {}))
     return Act(y, x.B * expand, x.f, x.h, x.w)
@@ -413,8 +417,9 @@ def adapter_block(P: Packed, p: str, x: Act, src, nb: Optional[int] = None, shar
     src: UNet edit-branch skip rows [(nb t N), C], or a list of nb row tensors [(t N), C] (the edit rows of the batch-4 skip, read in
     place).  Returns motion residual rows [(nb t N), C].
 
-    nb > x.B (x.B == 1): the ControlNet residual is SHARED by the nb batch entries (the reference feeds the
-    ControlNet the same edit latent twice, see pipelines.MotionEditorPipeline.dedup_controlnet).  Everything up to
+    nb > x.B: the ControlNet residual is SHARED -- entry k of x by the batch entries k, k + x.B, k + 2 x.B, ... of src (the reference feeds the
+    ControlNet the same edit latent twice, see pipelines.MotionEditorPipeline.dedup_controlnet: x.B = 1 entry for the two copies of the one edit
+    row, x.B = N entries for the edit rows [u.e_1 .. u.e_N, c.e_1 .. c.e_N] of N targets).  Everything up to
     the pose cross-attention depends on x only -- temporal convs, sparse-causal self-attention, cross_pose_norm,
     the pose query projection -- so it is computed once and READ by every batch entry: the attention kernel takes the shared
     queries (q_items), the GEMM epilogues the shared residuals (res_rows / res2_rows); nothing is copied."""
@@ -422,8 +427,8 @@ def adapter_block(P: Packed, p: str, x: Act, src, nb: Optional[int] = None, shar
     dh = C // HEADS
     nb = x.B if nb is None else nb
     share = nb != x.B
-    if share:
-        assert x.B == 1
+    if share and nb % x.B:
+        raise ValueError(f"adapter_block: {nb} batch entries cannot share {x.B} ControlNet entries")
     rows_x = t.shape[0]
     # conv path: TemporalConv(k=3) -> ReLU -> TemporalConv(k=1) -> + x, on independent chunks of 8 frames
     if shard is None:
@@ -539,10 +544,15 @@ def text_rows(ehs: torch.Tensor, dtype=torch.float16) -> torch.Tensor:
 
 def unet_forward(P: Packed, sample: torch.Tensor, t: float, ehs: torch.Tensor, *, down_res: Optional[Sequence[torch.Tensor]] = None,
                  mid_res: Optional[torch.Tensor] = None, two_branch: bool = False, spatial=None, temporal=None,
-                 taps: Optional[dict] = None, shard=None, normal_infer: bool = False, res_ready=None, side_stream=None, cfg_dup: bool = False) -> Act:
+                 taps: Optional[dict] = None, shard=None, normal_infer: bool = False, res_ready=None, side_stream=None, cfg_dup: bool = False,
+                 branches=None) -> Act:
     """sample: fp32 [B,4,f,h,w] (reference layout).  down_res: 12 row tensors [(2 f N_i), C_i] (two_branch,
     ControlNet batch = the two edit rows) or [(B f N_i), C_i]; mid_res rows [(2|B f N_3), 1280].
     Returns eps rows [(B f N), 4] as an Act.
+
+    branches (segments.Branches, default (rec, edit) pairs): which batch rows are edits and which row is each edit's source.  The editors and, with
+    two_branch, the adapter / residual scatter read it.  two_branch residuals hold one ControlNet entry per edit row, or fewer: the k-th edit row
+    reads entry k % entries (one entry for the two copies of the one edit row; N entries for the edit rows [u.e_1 .. u.e_N, c.e_1 .. c.e_N]).
 
     cfg_dup: the caller guarantees sample[B/2:] is a copy of sample[:B/2] (the pipeline's `torch.cat([latents] * 2)` for classifier-free
     guidance, pipeline_motion_editor.py:605).  The two halves then differ only through the text embedding, which first enters at the
@@ -552,13 +562,17 @@ def unet_forward(P: Packed, sample: torch.Tensor, t: float, ehs: torch.Tensor, *
     B, _, f, h, w = sample.shape
     dev = sample.device
     sample = sample.contiguous().float()
-    edit_rows = [b for b in range(B) if b % 2 == 1]   # batch = (recon, edit) pairs: 4 rows, or 2 on one CFG-parallel rank
+    if branches is None:
+        branches = segments.Branches.pairs(B)        # batch = (recon, edit) pairs: 4 rows, or 2 on one CFG-parallel rank
+    elif branches.B != B:
+        raise ValueError(f"unet_forward: the branch description covers {branches.B} rows, the batch has {B}")
+    edit_rows = list(branches.edit_rows)
     temb, toff = time_embedding(P, t, resnet_names(True), dev)
     text = text_rows(ehs, P.dtype)
     tseg = segments.cross_text(B, f, dev)
     # normal_infer (DDIM inversion, inference.py:292): attn1 = plain per-frame self-attention (attention_2d.py:770-777)
     kw = dict(spatial=spatial, temporal=temporal, shard=shard, sc_attn=not normal_infer,   # shard: this rank holds f = f_total / world consecutive frames
-              text_kv=text_kv_all(P, text, attention_block_names(True)))
+              text_kv=text_kv_all(P, text, attention_block_names(True)), branches=branches)
 
     # the CFG prefix (docstring): only when the spatial editor leaves the first self-attention alone (it does for start_layer > 0), un-sharded, not recording
     # (round 6: frame-sharded too -- `frames` mode holds the full batch of 4 on every rank; the prefix's exchanges then run at half the batch)
@@ -582,8 +596,10 @@ def unet_forward(P: Packed, sample: torch.Tensor, t: float, ehs: torch.Tensor, *
         r = down_res[i]
         if two_branch:   # adapter sees the edit rows only (unet_2d_condition.py:479-481): read in place, batch entry by batch entry
             n = s.f * s.N
-            shared = r.shape[0] == n and len(edit_rows) > 1   # one ControlNet entry shared by all edit rows
-            return adapter_block(P, f"controlnet_adapter.body.{i}", Act(r, 1 if shared else len(edit_rows), s.f, s.h, s.w), [s.rows_of(eb) for eb in edit_rows],
+            entries = r.shape[0] // n     # ControlNet entries: one per edit row, or fewer, shared -- the k-th edit row reads entry k % entries
+            if r.shape[0] != entries * n or not entries or len(edit_rows) % entries:
+                raise ValueError(f"unet_forward: ControlNet residual {i} has {r.shape[0]} rows, which {len(edit_rows)} edit rows of {n} rows cannot share")
+            return adapter_block(P, f"controlnet_adapter.body.{i}", Act(r, entries, s.f, s.h, s.w), [s.rows_of(eb) for eb in edit_rows],
                                  len(edit_rows), ashard)
         return adapter_block(P, f"controlnet_adapter.body.{i}", Act(r, s.B, s.f, s.h, s.w), s.t, None, ashard)   # (unet_2d_condition.py:483-485)
 
@@ -695,8 +711,9 @@ def unet_forward(P: Packed, sample: torch.Tensor, t: float, ehs: torch.Tensor, *
             plan.wait_event(torch.cuda.current_stream(), res_ready)
         if two_branch:
             nr = x.f * x.N
+            ne = mid_res.shape[0] // nr
             for k, eb in enumerate(edit_rows):
-                mk = mid_res[:nr] if mid_res.shape[0] == nr else mid_res[k * nr:(k + 1) * nr]   # shared or per-entry residual
+                mk = mid_res[(k % ne) * nr:(k % ne + 1) * nr]   # mid_res entry of the k-th edit row: its own, or one shared by its copies
                 ops.axpy_rows(x.rows_of(eb), x.rows_of(eb), mk)
         elif getattr(ops, "recording", False):
             x = x.like(ops.axpy_rows(torch.empty_like(x.t), x.t, mid_res))
@@ -747,10 +764,13 @@ def unet_forward(P: Packed, sample: torch.Tensor, t: float, ehs: torch.Tensor, *
 # ControlNet (diffusers 0.15.1 ControlNetModel.forward, called pipeline_motion_editor.py:618-625)
 # ---------------------------------------------------------------------------------------------
 def controlnet_forward(P: Packed, latents: torch.Tensor, lat_index: Sequence[int], t: float, prompt: torch.Tensor, cond: torch.Tensor,
-                       scale: float = 1.0, row_offset: int = 0):
+                       scale: float = 1.0, row_offset: int = 0, text_of_row: Optional[Sequence[int]] = None):
     """latents fp32 [nb,4,f,h,w]; lat_index: which latent row each ControlNet batch entry reads (the
     pipeline feeds rows [1,3] of cat([latents]*2), i.e. the edit latent twice); prompt [n_text,77,768]
-    with the reference's interleave (row r -> text r % n_text); cond fp32/fp16 [(nbc f),3,8h,8w].
+    with the reference's interleave (row r -> text r % n_text), or -- text_of_row, one entry per "(b f)" row -- the text row
+    every row reads spelt out (several targets: each entry interleaves its own target's pair); cond fp32/fp16 [(nbc f),3,8h,8w],
+    or the images of fewer entries ([(m f),3,8h,8w], m dividing nbc): entry j then reads image block j m / nbc (one skeleton
+    shared by all targets: its conditioning embedding is computed once).
     Returns (12 down residual row tensors [(nbc f N_i), C_i], mid rows), 2-D per-frame semantics."""
     nb, _, f, h, w = latents.shape
     nbc = len(lat_index)
@@ -759,7 +779,12 @@ def controlnet_forward(P: Packed, latents: torch.Tensor, lat_index: Sequence[int
     latents = latents.contiguous().float()
     temb, toff = time_embedding(P, t, resnet_names(False), dev)
     text = text_rows(prompt, P.dtype)
-    tseg = segments.cross_interleaved(nimg, prompt.shape[0], dev, row_offset)   # row_offset: this rank's first "(b f)" row in the full ControlNet batch
+    if text_of_row is not None:
+        if len(text_of_row) != nimg or row_offset or not all(0 <= r < prompt.shape[0] for r in text_of_row):
+            raise ValueError(f"controlnet_forward: text_of_row names one of the {prompt.shape[0]} text rows for each of the {nimg} rows of the un-sharded batch")
+        tseg = segments.cross_rows(text_of_row, dev)
+    else:
+        tseg = segments.cross_interleaved(nimg, prompt.shape[0], dev, row_offset)   # row_offset: this rank's first "(b f)" row in the full ControlNet batch
 
     # conditioning embedding: 3->16 (direct), then 16->16, 16->32 s2, 32->32, 32->96 s2, 96->96, 96->256 s2 (SiLU each), 256->320.
     # Everything up to the last convolution depends on the skeleton images only -- the same tensor in every denoising step of a run
@@ -767,7 +792,10 @@ def controlnet_forward(P: Packed, latents: torch.Tensor, lat_index: Sequence[int
     # (COND_EMBED_CACHE = False recomputes it every step, as the reference does).
     H8, W8 = cond.shape[-2], cond.shape[-1]
     cond = cond.contiguous()
-    ckey = (cond.data_ptr(), cond._version, tuple(cond.shape), cond.dtype, nimg)
+    ncond = cond.shape[0]                 # images held: those of all nbc entries, or of fewer (shared skeletons)
+    if ncond % f or not ncond or nbc % (ncond // f):
+        raise ValueError(f"controlnet_forward: {ncond} conditioning images for {nbc} entries of {f} frames")
+    ckey = (cond.data_ptr(), cond._version, tuple(cond.shape), cond.dtype, ncond)
     # one entry per conditioning tensor (address, version, shape), a handful at most: a captured step (denoise_step_graphed) bakes in the address of the
     # embedding it was captured with and holds a reference to it, so an entry that a later call with another skeleton pushes out of this table stays
     # alive for exactly as long as a graph can replay against it
@@ -777,7 +805,7 @@ def controlnet_forward(P: Packed, latents: torch.Tensor, lat_index: Sequence[int
         c = hit[0]
     else:
         c = Act(ops.conv_small(cond, P.mat32("controlnet_cond_embedding.conv_in.weight"), P.vec32("controlnet_cond_embedding.conv_in.bias"),
-                               n_img=nimg, Cin=3, H=H8, Wd=W8, img_stride=3 * H8 * W8, ch_stride=H8 * W8, silu=True), nimg, 1, H8, W8)
+                               n_img=ncond, Cin=3, H=H8, Wd=W8, img_stride=3 * H8 * W8, ch_stride=H8 * W8, silu=True), ncond, 1, H8, W8)
         for i in range(6):
             c = conv3x3(P, f"controlnet_cond_embedding.blocks.{i}", c, stride=2 if i % 2 == 1 else 1, act=2)
         if table is not None:
@@ -790,7 +818,15 @@ def controlnet_forward(P: Packed, latents: torch.Tensor, lat_index: Sequence[int
         part = ops.conv_small(latents[li], P.mat32("conv_in.weight"), P.vec32("conv_in.bias"), n_img=f, Cin=4, H=h, Wd=w,
                               img_stride=h * w, ch_stride=f * h * w)
         ops.copy_rows(x0[bi * f * h * w:(bi + 1) * f * h * w], part)
-    x = conv3x3(P, "controlnet_cond_embedding.conv_out", c, res=x0)
+    if ncond == nimg:
+        x = conv3x3(P, "controlnet_cond_embedding.conv_out", c, res=x0)
+    else:   # shared skeletons: the one embedding meets every entry's conv_in(sample) in a launch per entry (nothing is copied)
+        rc, rx, per = f * c.h * c.w, f * h * w, nbc // (ncond // f)
+        xo = torch.empty_like(x0)
+        for bi in range(nbc):
+            blk = bi // per
+            x = conv3x3(P, "controlnet_cond_embedding.conv_out", Act(c.t[blk * rc:(blk + 1) * rc], f, 1, c.h, c.w), res=x0[bi * rx:(bi + 1) * rx], out=xo[bi * rx:(bi + 1) * rx])
+        x = x.like(xo)
     x = Act(x.t, nimg, 1, h, w)
 
     tkv = text_kv_all(P, text, attention_block_names(False))

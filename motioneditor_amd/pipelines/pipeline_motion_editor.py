@@ -3,6 +3,10 @@
 rows, one batch-4 UNet3D forward with the content-aware motion adapter and both attention editors,
 classifier-free guidance and the DDIM update -- runs entirely on libmotioned HIP kernels.
 
+Several targets in one pass: ``pipe([source, t_1 .. t_N], latents=[1 + N, ...])`` (N <= 3) computes the reconstruction branch once per step -- the UNet batch is
+``[rec, e_1 .. e_N]`` per classifier-free-guidance half, ``.images[0]`` the reconstruction and ``.images[1:]`` the edits in prompt order, each what the two-prompt call
+of that target gives (the reference's driver runs the pipeline once per target, inference.py:298-323).
+
 Prompts are strings when the pipeline holds a ``text_encoder`` and a ``tokenizer``: the native
 ``models.clip.CLIPTextModel`` + ``tokenizer.CLIPTokenizer`` (libmotioned kernels, host-side BPE) or any pair with
 transformers' call surface.  With no ``text_encoder`` the prompt embeddings are passed as
@@ -19,7 +23,7 @@ from typing import Callable, List, Optional, Union
 
 import torch
 
-from .. import ops, plan
+from .. import ops, plan, segments
 from ..schedulers import DDIMScheduler
 
 
@@ -29,6 +33,15 @@ _LIVE_PIPELINES = weakref.WeakSet()   # every pipeline of this process: release_
 @dataclass
 class MotionEditorPipelineOutput:
     images: torch.Tensor
+
+
+MAX_TARGETS = segments.TATTN_MAX_BATCH // 2 - 1   # 2 (1 + N) batch rows per step; one temporal-attention launch holds 8 (me_tattn_args.kv_map)
+
+
+def _single_target_only(latents: torch.Tensor, what: str) -> None:
+    if latents.shape[0] > 2:
+        raise NotImplementedError(f"{what} runs one (recon, edit) pair: N > 1 targets (latents batch {latents.shape[0]} = 1 + N) are supported by "
+                                  "denoise_step and denoise_step_planned only")
 
 
 class MotionEditorPipeline:
@@ -246,6 +259,7 @@ class MotionEditorPipeline:
         additionally runs only one classifier-free-guidance half (rank 0 of the pair: the unconditional (recon, edit) rows,
         rank 1: the conditional ones), which halves every frame-shard exchange (batch 2 instead of 4); the pair trades its
         4-channel noise predictions with one all-gather before the fused CFG + DDIM update."""
+        _single_target_only(latents, "denoise_step_frame_sharded")
         if shard.f_total % 2:
             raise NotImplementedError("frame sharding relies on the ControlNet batch-entry identity, which needs an even frame count")
         f = latents.shape[2]
@@ -307,6 +321,7 @@ class MotionEditorPipeline:
         UNet / adapter / editors (GroupNorm statistics, K/V injection and the adapter all stay inside a pair), so the only
         exchange is ONE all-gather of the 4-channel noise prediction (RCCL over xGMI on MI355X; 2 x [2,4,f,h,w] fp16) before
         the fused CFG + DDIM update, which every rank then applies to its own copy of the latents."""
+        _single_target_only(latents, "denoise_step_cfg_parallel")
         from .. import parallel
         cx = parallel.exchange(group)                      # a torch process group, or an exchange adapter (direct RCCL for graph capture)
         r = cx.rank
@@ -332,8 +347,20 @@ class MotionEditorPipeline:
     def denoise_step(self, latents: torch.Tensor, t: int, text_embeddings_input: torch.Tensor, images: Optional[torch.Tensor],
                      guidance_scale: float, controlnet_conditioning_scale: float = 1.0, taps: Optional[dict] = None) -> torch.Tensor:
         """One iteration of the reference loop body (:603-648).  latents fp32 [2,4,f,h,w] = [recon, edit];
-        text_embeddings_input [4,77,768] = [uncond, uncond, cond_recon, cond_edit]."""
+        text_embeddings_input [4,77,768] = [uncond, uncond, cond_recon, cond_edit].
+
+        Several targets in one pass: latents [1+N,4,f,h,w] = [recon, edit_1 .. edit_N], text_embeddings_input [2(1+N),77,768] = [uncond x (1+N),
+        cond_recon, cond_edit_1 .. cond_edit_N], images [(2 N f),3,H,W] = the N targets' skeletons, twice (or [(2 f),3,H,W]: one skeleton shared by
+        all targets).  Row k of the result is what the two-row step of (recon, edit_k) gives: the UNet batch is [rec, e_1 .. e_N] per
+        classifier-free-guidance half, described to the graph and the editors by segments.Branches.targets(N); N = 1 is the two-row step itself."""
         nb = latents.shape[0]
+        nt = nb - 1                                # targets
+        if text_embeddings_input.shape[0] != 2 * nb:
+            raise ValueError(f"denoise_step: {nb} latent rows need {2 * nb} text-embedding rows [uncond x {nb}, cond x {nb}], got {text_embeddings_input.shape[0]}")
+        if nt > MAX_TARGETS:
+            raise ValueError(f"denoise_step: at most {MAX_TARGETS} targets per call (the UNet batch 2 (1 + N) must fit the {segments.TATTN_MAX_BATCH} batch rows "
+                             f"of one temporal-attention launch), got N = {nt}")
+        branches = segments.Branches.targets(nt) if nt > 1 else None     # None: the (recon, edit) pair, today's path
         # :605 (scale_model_input is the identity for DDIM); on the GPU the duplication is two library copies, so that a recorded step holds no torch kernel
         native = latents.is_cuda and getattr(ops, "NATIVE", False) and latents.dtype == torch.float32 and latents.is_contiguous()
         if not native:
@@ -342,11 +369,26 @@ class MotionEditorPipeline:
         down = mid = ready = None
         two = False
         if self.controlnet is not None and images is not None:
-            prompt = text_embeddings_input[1::2]                         # :615; .repeat(f,1,1) on "(b f)" rows -> row r reads r % 2 (:621)
             f = latents.shape[2]
+            dedup = self.dedup_controlnet and f % 2 == 0
+            if branches is None:
+                prompt = text_embeddings_input[1::2]                     # :615; .repeat(f,1,1) on "(b f)" rows -> row r reads r % 2 (:621)
+            else:
+                # One ControlNet entry per target (the two guidance copies of an edit row are one entry when f is even, as for the pair), or per
+                # (guidance copy, target).  Entry j = copy j // N of target j % N reads, at frame g, the text row that the two-prompt call of that target
+                # reads there: "(b f)" row r = copy * f + g of ITS batch -> r % 2 of (uncond row of e_k, cond row of e_k) (:615,621).
+                prompt = text_embeddings_input
+                entries = list(range(1, nb)) if dedup else [b for b in range(2 * nb) if b % nb]
+                text_of_row = [((j // nt) * f + g) % 2 * nb + 1 + j % nt for j in range(len(entries)) for g in range(f)]
+                if images.shape[0] not in (2 * f, 2 * nt * f):
+                    raise ValueError(f"denoise_step: expected the skeletons of {nt} targets, twice ({2 * nt * f} images), or one shared skeleton, twice "
+                                     f"({2 * f}), got {images.shape[0]} images")
 
             def run_controlnet():
-                if self.dedup_controlnet and f % 2 == 0:
+                if branches is not None:
+                    return self.controlnet.forward_rows(x4, entries, t, prompt, images[:images.shape[0] // 2] if dedup else images,
+                                                        controlnet_conditioning_scale, text_of_row=text_of_row)
+                if dedup:
                     # one entry; the UNet graph broadcasts it to both edit rows (and shares the adapter's x-only half)
                     return self.controlnet.forward_rows(x4, [1], t, prompt, images[:images.shape[0] // 2], controlnet_conditioning_scale)
                 return self.controlnet.forward_rows(x4, [1, 3], t, prompt, images, controlnet_conditioning_scale)   # :613-625
@@ -368,7 +410,7 @@ class MotionEditorPipeline:
                 taps["cn_down"], taps["cn_mid"] = [d.clone() for d in down], mid.clone()
         eps = self.unet.forward_rows(x4, t, text_embeddings_input, down, mid, two, taps, res_ready=ready,
                                      side_stream=self._side_stream if (ready is not None and self.overlap_adapter) else None,
-                                     cfg_dup=self.dedup_cfg_prefix and nb * 2 == x4.shape[0])   # :632-640
+                                     cfg_dup=self.dedup_cfg_prefix and nb * 2 == x4.shape[0], branches=branches)   # :632-640
         if taps is not None:
             taps["eps_rows"] = eps.t.clone()
         ca, cb = self.scheduler.coeffs(int(t))
@@ -394,6 +436,7 @@ class MotionEditorPipeline:
         `cfg_parallel_group=` -> `denoise_step_cfg_parallel`.  Collectives are captured as graph nodes (torch.distributed's NCCL/RCCL
         process group enqueues on its streams, which fork from and join the capturing stream); every rank of the groups involved must
         capture and replay in step."""
+        _single_target_only(latents, "denoise_step_graphed")
         from .. import parallel
         sed, ted = self.unet.spatial_editor, self.unet.temporal_editor
         if shard is not None:
@@ -545,8 +588,16 @@ class MotionEditorPipeline:
         batch_size = 1 if isinstance(prompt, str) else len(prompt)
         device = self._execution_device
         do_cfg = guidance_scale > 1.0
-        if not do_cfg or batch_size != 2:
-            raise NotImplementedError("the two-branch hot path needs guidance_scale > 1 and prompts = [source, target] (inference.py:296-323)")
+        if not do_cfg or batch_size < 2:
+            raise NotImplementedError("the two-branch hot path needs guidance_scale > 1 and prompts = [source, target_1, ..., target_N], N >= 1 "
+                                      "(inference.py:296-323 runs them one call per target)")
+        n_targets = batch_size - 1
+        if n_targets > MAX_TARGETS:
+            raise ValueError(f"at most {MAX_TARGETS} targets per call ({1 + MAX_TARGETS} prompts: the UNet batch 2 (1 + N) must fit the "
+                             f"{segments.TATTN_MAX_BATCH} batch rows of one temporal-attention launch), got {n_targets}")
+        if latents is not None and latents.shape[0] != batch_size * num_videos_per_prompt:
+            raise ValueError(f"`latents` must hold {batch_size * num_videos_per_prompt} rows = [source, target_1 .. target_{n_targets}] (the inversion latent repeated, "
+                             f"inference.py:296), got {latents.shape[0]}")
         with_uncond = do_cfg if uncond_embeddings is None else False
         text_embeddings = self._encode_prompt(prompt, device, num_videos_per_prompt, with_uncond, negative_prompt, kwargs.get("text_embeddings"),
                                               kwargs.get("negative_text_embeddings"))
@@ -557,7 +608,16 @@ class MotionEditorPipeline:
         if self.controlnet is not None:
             if skeleton is None:
                 raise ValueError("skeleton is required with a ControlNet (pipeline :556)")
-            target = torch.unsqueeze(skeleton[-1], dim=0)                   # :556
+            if n_targets == 1 or len(skeleton) != 2 * batch_size:
+                # one target, or several that share one skeleton (inference.py:300-302 passes the same 4 entries for every prompt): the last entry
+                if n_targets > 1 and len(skeleton) != 4:
+                    raise ValueError(f"`skeleton` must hold {2 * batch_size} entries [0, s_1 .. s_{n_targets}, 0, s_1 .. s_{n_targets}] (one skeleton per target) "
+                                     f"or 4 entries (one skeleton shared by all targets), got {len(skeleton)}")
+                target = torch.unsqueeze(skeleton[-1], dim=0)               # :556
+            else:                                                           # the reference's pattern for 1 + N prompts: target k's skeleton is entry (1 + N) + k
+                target = skeleton[batch_size + 1:]
+                if not isinstance(target, torch.Tensor):
+                    target = torch.stack(list(target))
             images = self.prepare_image(target, width, height, 1 * num_images_per_prompt, num_images_per_prompt, device, torch.float32, do_cfg)
             images = images.reshape(-1, *images.shape[2:]).contiguous()    # "b f c h w -> (b f) c h w" (:570)
 

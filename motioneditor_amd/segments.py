@@ -5,11 +5,48 @@ same tables are replayed every step.
 """
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from dataclasses import dataclass
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from .capi import SEG_DUAL_BIN, SEG_DUAL_CUR, SEG_DUAL_PREV, SEG_PLAIN
+
+TATTN_MAX_BATCH = 8   # me_tattn_args.kv_map has 8 entries (include/motioned.h): the batch rows one temporal-attention launch holds
+
+
+@dataclass(frozen=True)
+class Branches:
+    """Which rows of a UNet batch are reconstruction rows and which are edits, carried beside the batch: src[b] = the row whose K | V the editors
+    inject into row b -- b itself for a reconstruction row, its source row for an edit.  An edit never names another edit."""
+    src: Tuple[int, ...]
+
+    def __post_init__(self):
+        for b, s in enumerate(self.src):
+            if not 0 <= s < len(self.src) or self.src[s] != s:
+                raise ValueError(f"Branches: row {b} names source {s}, which is not a reconstruction row of a batch of {len(self.src)}")
+
+    @staticmethod
+    def pairs(B: int) -> "Branches":
+        """(rec, edit) pairs: batch 4 = [u.rec, u.edit, c.rec, c.edit] (fully_control.py:439-441), batch 2 = one pair on a CFG-parallel rank."""
+        return Branches(tuple(b - b % 2 for b in range(B)))
+
+    @staticmethod
+    def targets(n: int, halves: int = 2) -> "Branches":
+        """One source and n targets per classifier-free-guidance half: [rec, e_1 .. e_n] x halves.  n = 1 is pairs(2 * halves)."""
+        return Branches(tuple(h * (1 + n) for h in range(halves) for _ in range(1 + n)))
+
+    @property
+    def B(self) -> int:
+        return len(self.src)
+
+    @property
+    def edit_rows(self) -> Tuple[int, ...]:
+        return tuple(b for b, s in enumerate(self.src) if s != b)
+
+    def edits_of(self, s: int) -> Tuple[int, ...]:
+        return tuple(b for b, sb in enumerate(self.src) if sb == s and b != s)
+
 
 _cache: Dict[Tuple, Tuple[torch.Tensor, torch.Tensor]] = {}
 GENERAL_DUAL: Dict[int, bool] = {}  # seg_mode.data_ptr() -> table uses the general (mask-reading) dual modes
@@ -55,6 +92,12 @@ def cross_interleaved(n_items: int, n_text: int, device, row_offset: int = 0):
     return _mk(("crossil", n_items, n_text, row_offset), [[(i + row_offset) % n_text] for i in range(n_items)], [[SEG_PLAIN]] * n_items, device)
 
 
+def cross_rows(text_of_item: Sequence[int], device):
+    """item i attends text row text_of_item[i]: the ControlNet prompt quirk of cross_interleaved, spelt out item by item for several targets."""
+    t = tuple(int(x) for x in text_of_item)
+    return _mk(("crossrows", t), [[x] for x in t], [[SEG_PLAIN]] * len(t), device)
+
+
 def _gi(shard, B, f):
     """(b, GLOBAL frame) -> kv item index: plain (b*f + g) unsharded; when sharded, whatever layout the shard view gives the
     gathered K|V (parallel.FrameShard: part-major all-gather; parallel.PrevFrameHalo: [halo | local])."""
@@ -86,29 +129,37 @@ def first_prev_chunked(B: int, f: int, chunk: int, device, shard=None):
     return _mk(("firstprev", B, f, chunk) + key, rows, [[SEG_PLAIN, SEG_PLAIN]] * (B * f), device, ref_units=2 * B * f)
 
 
-def edited_spatial(f: int, device, binary_mask: bool = False, B: int = 4, shard=None):
+def edited_spatial(f: int, device, binary_mask: bool = False, B: int = 4, shard=None, branches: Optional[Branches] = None):
     """FullySelfAttentionControlMask on batch 4 = [u.rec, u.edit, c.rec, c.edit] (fully_control.py:425-447;
     B = 2 is one (rec, edit) pair, i.e. one classifier-free-guidance half on a CFG-parallel rank):
     recon rows keep [prev | cur]; edit rows attend [src prev (fg/bg dual, mask frame max(head-1,0)) |
     src cur (dual, mask frame head) | own cur]; the edit branch's prev-frame K/V are dropped
     (k[:, 3N:], fully_control.py:383).  With a binary mask (the reference's man.mask PNGs are 0/255) the
     fg/bg pair of every source key weighs exp(s) + exp(0) whichever way the bit points, so the kernel's
-    DUAL_BIN mode needs no mask read."""
+    DUAL_BIN mode needs no mask read.
+
+    branches (default Branches.pairs(B)): which rows are edits and of which source -- with several targets every edit of every target reads the ONE
+    source of its half, same mask planes, same modes.  The binary-dual column sums of V are per kv item (ops.attention), hence computed once per
+    source item however many edits read it."""
+    br = Branches.pairs(B) if branches is None else branches
+    if br.B != B:
+        raise ValueError(f"edited_spatial: the branch description covers {br.B} rows, the batch has {B}")
     gi, f0, key = _gi(shard, B, f)
     rows, modes = [], []
     for b in range(B):
+        s = br.src[b]
         for i in range(f):
             g = f0 + i
-            if b % 2 == 0:
+            if s == b:
                 rows.append([gi(b, max(g - 1, 0)), gi(b, g), -1])
                 modes.append([SEG_PLAIN, SEG_PLAIN, SEG_PLAIN])
             else:
-                rows.append([gi(b - 1, max(g - 1, 0)), gi(b - 1, g), gi(b, g)])
+                rows.append([gi(s, max(g - 1, 0)), gi(s, g), gi(b, g)])
                 modes.append([SEG_DUAL_BIN, SEG_DUAL_BIN, SEG_PLAIN] if binary_mask else [SEG_DUAL_PREV, SEG_DUAL_CUR, SEG_PLAIN])
-    # processing order: (recon frame i, edit frame i, recon frame i + 1, ...) per (recon, edit) pair -- an edit item reads its source's K | V right after
-    # the reconstruction item did, while they are still in the XCD's L2 (ascending order puts f items between the two)
-    order = [b * f + i + r * f for b in range(0, B - 1, 2) for i in range(f) for r in (0, 1)] + ([(B - 1) * f + i for i in range(f)] if B % 2 else [])
-    return _mk(("edited", f, binary_mask, B) + key, rows, modes, device, order=order)
+    # processing order: (source frame i, every edit's frame i, source frame i + 1, ...) per source -- the edit items read their source's K | V right after
+    # the reconstruction item did, while they are still in the XCD's L2 (ascending order puts f items between a source and its first reader)
+    order = [b * f + i for s in range(B) if br.src[s] == s for i in range(f) for b in (s,) + br.edits_of(s)]
+    return _mk(("edited", f, binary_mask, B) + (() if br == Branches.pairs(B) else (br.src,)) + key, rows, modes, device, order=order)
 
 
 def has_dual(seg_mode: torch.Tensor) -> bool:

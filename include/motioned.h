@@ -193,7 +193,8 @@ typedef struct me_attn_args {
   const int32_t* seg_item; /* device int32 [n_items][nseg]: kv item index of each segment; a negative
                               entry ends the item's segment list (skipped segments must come last) */
   const int32_t* seg_mode; /* device int32 [n_items][nseg]: ME_SEG_*                       */
-  const void* mask;        /* fp16 [8][nk] mask planes (only for DUAL_CUR / DUAL_PREV)     */
+  const void* mask;        /* fp16 [8][nk] mask planes (only for DUAL_CUR / DUAL_PREV, which read plane `head` / `head - 1`: such a launch
+                              needs mask != NULL and heads <= 8) */
   float scale;
   int32_t general_dual;    /* 1 when any seg_mode is DUAL_CUR / DUAL_PREV (selects the kernel built with that path) */
   /* Required when any seg_mode is ME_SEG_DUAL_BIN: device scratch of me_attn_vsum_bytes(n_kv_items, heads*dh) bytes, 16-byte
@@ -243,7 +244,9 @@ typedef struct me_tattn_args {
   void* O;
   int32_t ldq, ldk, ldv, ldo;
   int32_t heads, dh;
-  int32_t batch, frames, npix; /* frames (of K/V) in {8,16,24,32,40,48} */
+  int32_t batch, frames, npix; /* dh 40 / 80 / 160: any frames (of K/V) <= 64, the MFMA form ("tattn_mfma_kernel<dh,32|64>").  Every other dh that
+                                  divides 320 (and frames > 64): the per-thread form ("tattn_kernel<frames>"), frames in {8,16,24,32,40,48} and
+                                  (320 / dh) * query frames <= 512 -- one thread per (head of a 320-column slice, query frame) */
   int32_t kv_map[8];           /* batch <= 8 */
   float scale;
   /* frame sharding: Q/O hold q_frames local frames starting at global frame q_frame0 (0, 0 = all frames);

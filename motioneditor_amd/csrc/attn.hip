@@ -1446,6 +1446,7 @@ extern "C" int me_attn(const me_attn_args* a, void* stream) {
   if (a->ldq % 8 || a->ldk % 8 || a->ldv % 8 || a->ldo % 4) { me_set_error("me_attn: row strides must be multiples of 8 (Q,K,V) / 4 (O)"); return ME_EINVAL; }
   if (((uintptr_t)a->Q | (uintptr_t)a->K | (uintptr_t)a->V) & 15 || ((uintptr_t)a->O & 7)) { me_set_error("me_attn: misaligned pointer"); return ME_EINVAL; }
   if (a->q_items < 0 || (a->general_dual && (a->q_items > 0 || a->lse))) { me_set_error("me_attn: q_items / lse are not served by the general-dual kernel"); return ME_EINVAL; }
+  if (a->general_dual && (!a->mask || a->heads > 8 || ((uintptr_t)a->mask & 1))) { me_set_error("me_attn: the general-dual kernel reads mask plane `head` of fp16 [8][nk]: mask != NULL, heads <= 8"); return ME_EINVAL; }
   if (a->lse && a->vsum) { me_set_error("me_attn: lse is written for plain segments only"); return ME_EINVAL; }
   if (a->hsk < 0 || a->hsv < 0 || a->hsq < 0 || a->hsk % 8 || a->hsv % 8 || a->hsq % 8) { me_set_error("me_attn: head strides must be non-negative multiples of 8"); return ME_EINVAL; }
   if (a->item_order && ((uintptr_t)a->item_order & 3)) { me_set_error("me_attn: misaligned item_order"); return ME_EINVAL; }

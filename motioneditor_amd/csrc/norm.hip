@@ -437,7 +437,8 @@ static int gn_validate(const me_groupnorm_args* a) {
   if (!a || !a->X || !a->Y || !a->gamma || !a->beta || !a->stats) { me_set_error("me_groupnorm: null pointer"); return ME_EINVAL; }
   if (a->rows <= 0 || a->rows_per_group <= 0 || a->rows % a->rows_per_group) { me_set_error("me_groupnorm: rows must be a multiple of rows_per_group"); return ME_EINVAL; }
   if (a->groups <= 0 || a->groups > 64 || a->C % a->groups || a->C % 8 || a->ldx % 8 || a->ldy % 8) { me_set_error("me_groupnorm: bad channel geometry"); return ME_EINVAL; }
-  if (((uintptr_t)a->X | (uintptr_t)a->Y | (uintptr_t)a->gamma | (uintptr_t)a->beta) & 15) { me_set_error("me_groupnorm: misaligned pointer"); return ME_EINVAL; }
+  // (stats: the float4 partial sums of the chunks follow the fp64 statistics)
+  if (((uintptr_t)a->X | (uintptr_t)a->Y | (uintptr_t)a->gamma | (uintptr_t)a->beta | (uintptr_t)a->stats) & 15) { me_set_error("me_groupnorm: misaligned pointer"); return ME_EINVAL; }
   return ME_OK;
 }
 

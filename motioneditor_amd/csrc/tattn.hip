@@ -8,8 +8,11 @@
 // in registers, K/V come from LDS (the F lanes of a head read the same address -> broadcast).
 #include "me_common.h"
 #include "../../include/motioned.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <utility>
+
+extern "C" void me_set_kernel(const char* name);
 
 namespace {
 
@@ -280,6 +283,11 @@ int launch_tattn_mfma(const me_tattn_args* a, hipStream_t st) {
   const long blocks = (long)a->batch * a->npix * nslice;
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL((tattn_mfma_kernel<DH, KP>), dim3((unsigned)blocks), dim3(64 * (SLICE / DH)), 0, st, *a);
+  {
+    char nm[64];
+    snprintf(nm, sizeof(nm), "tattn_mfma_kernel<%d,%d>", DH, KP);
+    me_set_kernel(nm);
+  }
   return hipGetLastError() == hipSuccess ? ME_OK : ME_EHIP;
 }
 
@@ -300,6 +308,11 @@ int launch_tattn(const me_tattn_args* a, hipStream_t st) {
   }
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(tattn_kernel<F>, dim3((unsigned)blocks), dim3(threads), lds, st, *a);
+  {
+    char nm[64];
+    snprintf(nm, sizeof(nm), "tattn_kernel<%d>", F);
+    me_set_kernel(nm);
+  }
   return hipGetLastError() == hipSuccess ? ME_OK : ME_EHIP;
 }
 
@@ -329,6 +342,12 @@ extern "C" int me_tattn(const me_tattn_args* a, void* stream) {
     }
     if (rc != ME_OK) me_set_error("me_tattn: kernel launch failed");
     return rc;
+  }
+  if (a->frames < 8 || a->frames > 48 || a->frames % 8) { me_set_error("me_tattn: frames must be one of 8,16,24,32,40,48"); return ME_EINVAL; }
+  // the per-thread kernel: one thread per (head of the slice, query frame), built for blocks of up to 512 threads
+  if ((SLICE / a->dh) * (a->q_frames > 0 ? a->q_frames : a->frames) > 512) {
+    me_set_error("me_tattn: the per-thread kernel serves (320 / dh) * query frames <= 512 threads per block");
+    return ME_EINVAL;
   }
   switch (a->frames) {
     case 8: rc = launch_tattn<8>(a, st); break;

@@ -168,7 +168,7 @@ def gemm(x: torch.Tensor, w: torch.Tensor, *, M: Optional[int] = None, out: Opti
                 or cs_.dtype != torch.float32 or cv_.dtype != torch.float32 or cs_.numel() != N or cv_.numel() != N or not cs_.is_contiguous() or not cv_.is_contiguous():
             raise ValueError("gemm: ln = (fp32 stats [parts, rows, 2], fp32 colsum [N], fp32 cvec [N], eps)")
         a.ln_stats, a.ln_colsum, a.ln_cvec, a.ln_eps = st_.data_ptr(), cs_.data_ptr(), cv_.data_ptr(), eps_
-        a.ln_parts, a.ln_stride = st_.shape[0], st_.stride(0)
+        a.ln_parts, a.ln_stride = st_.shape[0], (st_.stride(0) if st_.shape[0] > 1 else 2 * st_.shape[1])   # (one part: torch's stride of a size-1 dimension means nothing)
     so = None
     if ln_out:
         if panels is not None or geglu:
@@ -325,13 +325,17 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, heads: int, 
 
 def temporal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, heads: int, dh: int, batch: int, frames: int, npix: int,
                        kv_map: Optional[Sequence[int]] = None, scale: Optional[float] = None, q_frames: int = 0, q_frame0: int = 0,
-                       kv_parts: int = 1, q_parts: int = 1) -> torch.Tensor:
+                       kv_parts: int = 1, q_parts: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """frames = K/V frames.  Frame-sharded: q holds q_frames local frames from global frame q_frame0; k, v are the
     all-gather (part-major) of kv_parts equal frame shards.  Pixel-sharded (after the frame<->pixel all-to-all): q, k, v and
     the output all hold every frame of this rank's npix pixels, part-major (q_parts == kv_parts)."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _chk2d(t, "temporal_attention." + n)
-    out = empty(batch * (q_frames or frames) * npix, heads * dh, q)
+    if out is None:
+        out = empty(batch * (q_frames or frames) * npix, heads * dh, q)
+    _chk2d(out, "temporal_attention.out")
+    if out.shape[0] < batch * (q_frames or frames) * npix or out.shape[1] < heads * dh:
+        raise ValueError("temporal_attention: out too small")
     a = TAttnArgs()
     a.Q, a.K, a.V, a.O = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
     a.ldq, a.ldk, a.ldv, a.ldo = q.stride(0), k.stride(0), v.stride(0), out.stride(0)
@@ -380,9 +384,13 @@ def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, rows_
     return out
 
 
-def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
+def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk2d(x, "layernorm.x")
-    out = empty(x.shape[0], x.shape[1], x)
+    if out is None:
+        out = empty(x.shape[0], x.shape[1], x)
+    _chk2d(out, "layernorm.out")
+    if out.shape != x.shape:
+        raise ValueError("layernorm: out must have the shape of x")
     a = LayerNormArgs()
     a.X, a.Y, a.gamma, a.beta = x.data_ptr(), out.data_ptr(), gamma.data_ptr(), beta.data_ptr()
     a.rows, a.C, a.ldx, a.ldy, a.eps = x.shape[0], x.shape[1], x.stride(0), out.stride(0), eps

@@ -32,11 +32,27 @@ def _r16(t):
 # ------------------------------------------------------------------------------------------------------------------ forwards (fp64, differentiable)
 def _gather_gemm(x, w, *, M, alpha=1.0, conv=None, tconv=None):
     """y[:M] = alpha * gather(x) @ w^T of me_gemm: w [N, taps, K]; conv = (Hin, Win, Hout, Wout, stride, ups) is the 3 x 3, pad-1 convolution on channels-last
-    rows (ups = 1: over the nearest-2x upsample of the input); tconv = (frames, npix, chunk) the 3-tap TemporalConv whose taps stay inside a chunk of frames."""
+    rows (ups = 1: over the nearest-2x upsample of the input); tconv = (frames, npix, chunk) the 3-tap TemporalConv whose taps stay inside a chunk of frames.
+    The forward sweep (tests/ref64_fwd.py) adds: conv[6] = pad0 (1: no padding at the top / left), ups = 3 (w [N, 16, K]: the four 2x2-tap convolutions of
+    the folded nearest-2x form, one per output parity) and the frame-sharded tconv = (frames, npix, chunk, frame0, frames_total, halo_prev, halo_next)."""
     N, taps, K = w.shape
     x = x[:, :K]
-    if conv is not None:
+    if conv is not None and conv[5] == 3:
+        Hin, Win, Hout, Wout = conv[:4]
+        n_img = x.shape[0] // (Hin * Win)
+        img = x[:n_img * Hin * Win].reshape(n_img, Hin, Win, K)
+        pad = torch.zeros((n_img, Hin + 2, Win + 2, K), dtype=D)
+        pad[:, 1:-1, 1:-1] = img                                   # padded pixel (y + 1, x + 1) = pixel (y, x)
+        y = torch.zeros((n_img, Hout, Wout, N), dtype=D)
+        for py in range(2):
+            for px in range(2):
+                for ty in range(2):
+                    for tx in range(2):                            # tap (ty, tx) of parity (py, px) reads pixel (y + py - 1 + ty, x + px - 1 + tx)
+                        y[:, py::2, px::2] += pad[:, py + ty:py + ty + Hin, px + tx:px + tx + Win] @ w[:, 4 * (2 * py + px) + 2 * ty + tx].t()
+        y = y.reshape(-1, N)
+    elif conv is not None:
         Hin, Win, Hout, Wout, stride, ups = conv[:6]
+        pad0 = conv[6] if len(conv) > 6 else 0
         n_img = x.shape[0] // (Hin * Win)
         img = x[:n_img * Hin * Win].reshape(n_img, Hin, Win, K)
         if ups == 1:
@@ -44,6 +60,8 @@ def _gather_gemm(x, w, *, M, alpha=1.0, conv=None, tconv=None):
         Hv, Wv = img.shape[1], img.shape[2]
         pad = torch.cat([torch.zeros((n_img, 1, Wv, K), dtype=D), img, torch.zeros((n_img, 1, Wv, K), dtype=D)], dim=1)
         pad = torch.cat([torch.zeros((n_img, Hv + 2, 1, K), dtype=D), pad, torch.zeros((n_img, Hv + 2, 1, K), dtype=D)], dim=2)
+        if pad0:                                                   # F.pad(x, (0, 1, 0, 1)): the window starts at the pixel itself
+            pad = pad[:, 1:, 1:]
         y = None
         for ky in range(3):
             for kx in range(3):
@@ -51,6 +69,24 @@ def _gather_gemm(x, w, *, M, alpha=1.0, conv=None, tconv=None):
                 t = sl @ w[:, ky * 3 + kx].t()
                 y = t if y is None else y + t
         y = y.reshape(-1, N)
+    elif tconv is not None and len(tconv) > 3:
+        frames, npix, chunk, frame0, ftot, hp, hn = tconv
+        nb = M // (frames * npix)
+        t = x[:nb * frames * npix].reshape(nb, frames, npix, K)
+        outs = []
+        for fr in range(frames):
+            acc = torch.zeros((nb, npix, N), dtype=D)
+            for tap in range(3):
+                gs, ls = frame0 + fr + tap - 1, fr + tap - 1
+                if gs < 0 or gs >= ftot or gs // chunk != (frame0 + fr) // chunk:
+                    continue
+                if 0 <= ls < frames:
+                    acc = acc + t[:, ls] @ w[:, tap].t()
+                elif (hp if ls < 0 else hn) >= 0:                  # the one-frame halo appended to x (no halo given: the tap contributes nothing)
+                    h0 = hp if ls < 0 else hn
+                    acc = acc + x[h0:h0 + nb * npix].reshape(nb, npix, K) @ w[:, tap].t()
+            outs.append(acc)
+        y = torch.stack(outs, dim=1).reshape(-1, N)
     elif tconv is not None:
         frames, npix, chunk = tconv[:3]
         nb = x.shape[0] // (frames * npix)

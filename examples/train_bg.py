@@ -9,6 +9,10 @@ and the tuned UNet written as checkpoint-<steps>/model.safetensors -- what train
 (resume_from_checkpoint) read.
 
     python examples/train_bg.py [--frames 8 --size 512 --steps 3 --lr 3e-5 --out runs/bg] [--prompt "a girl is dancing" [--checkpoint SD15_DIR]]
+--trainable-modules M [M ...]: train_bg.py's `trainable_modules` (module-path suffixes; default attn1.to_q attn2.to_q attn_temp).  Beside the dense
+transformer-block projections the tuner takes the 3x3 convolutions of the residual blocks and the down- / upsamplers, conv_shortcut, proj_in / proj_out and
+the GroupNorm affine parameters, e.g. `--trainable-modules attn1.to_q attn2.to_q attn_temp .conv1 .conv2 resnets.0.norm1` (a bare `conv1` would also match
+temp_conv1, which -- like time_emb_proj, the time embedding, conv_in / conv_out and the LayerNorms -- is refused by name).
 --prompt: `encoder_hidden_states = text_encoder(prompt_ids)[0]` (:333) with the native CLIP classes instead of a synthetic embedding.
 --video-dir DIR [--mask-dir man.mask --condition openposefull --suffix .png]: pixel_values come from data.dataset.VideoDataset (train_bg.py:323) instead of
 synthetic tensors; --frames and --size are its n_sample_frames and width / height.
@@ -53,6 +57,8 @@ def main() -> None:
     ap.add_argument("--out", default="runs/bg")
     ap.add_argument("--prompt", default=None, help="encode this prompt with the native CLIP text encoder instead of a synthetic embedding")
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
+    ap.add_argument("--trainable-modules", nargs="+", default=["attn1.to_q", "attn2.to_q", "attn_temp"], metavar="M",
+                    help="train_bg.py's trainable_modules: every parameter under a module whose path ends with one of these is trained")
     add_clip_arguments(ap)
     args = ap.parse_args()
     from motioneditor_amd import util
@@ -60,7 +66,7 @@ def main() -> None:
     from motioneditor_amd.models.vae import AutoencoderKL
     dev = "cuda"
     vae, unet = AutoencoderKL.from_synthetic(dev), UNet2DConditionModel.from_synthetic(dev)
-    tuner = util.UNetTuner(unet, lr=args.lr)
+    tuner = util.UNetTuner(unet, trainable_modules=tuple(args.trainable_modules), lr=args.lr)
     print(f"training {len(tuner.names)} parameters ({tuner.master.numel() / 1e6:.1f} M values); {len(tuner.unreached)} selected parameters of the "
           "adapter are not reached by this forward and stay frozen")
     ehs = encode_prompt(args.prompt, args.checkpoint, dev) if args.prompt is not None else None

@@ -11,11 +11,11 @@ and `out=` targets accumulate where they belong without any graph surgery.
 The primitives (`ops.gemm_dx`, `ops.geglu_bwd`, `ops.attention_bwd`, `ops.temporal_attention_bwd`, `ops.groupnorm_bwd`,
 `ops.layernorm_bwd`, and for trained parameters `ops.gemm_dw`, `ops.colsum_grad`, `ops.layernorm_bwd_params`, `ops.relu_bwd`) are the
 kernel-level contract of the backward pass; every accumulation into a gradient buffer goes through `ops.grad_acc`.  On the GPU each is a
-HIP kernel of libmotioned (csrc/bwd.hip, attn_bwd.hip, train.hip) or me_gemm itself on transposed weights; tests/emu_ops.py states them on
+HIP kernel of libmotioned (csrc/bwd.hip, attn_bwd.hip, train.hip, tune.hip) or me_gemm itself on transposed weights; tests/emu_ops.py states them on
 the CPU (each as the vector-Jacobian product of its forward emulation) and pins this module, through `util.null_optimization` and
 `util.adapter_training_grads`, against the reference's own optimisation (tests/golden/null_text.npz, adapter_train.npz).  Still raising
-(not differentiated): edited / masked attention segments, shared query items, sharded row orders, the temporal editor's kv_map, the
-pad-(0,1,0,1) convolution and 3x3-convolution weights.
+(not differentiated): edited / masked attention segments, shared query items, sharded row orders, the temporal editor's kv_map and the
+pad-(0,1,0,1) convolution.
 
 Restrictions (asserted): single assignment -- no allocation region is written twice while recording (true for the
 single-branch UNet forward; the in-place motion / ControlNet residual adds of the two-branch step are not differentiated).
@@ -86,6 +86,15 @@ class Grads:
                 g = self.params[k] = torch.zeros((r1 - r0, *t.shape[1:]), dtype=torch.float32, device=t.device)
             out.append((r0, r1, g))
         return out
+
+    def param_whole(self, t: torch.Tensor) -> torch.Tensor:
+        """The gradient buffer of a tensor that is trained WHOLE, whichever way `trainable` names it (a key, or one row range that covers it)."""
+        rows = self.param_rows(t)
+        if rows is None:
+            return self.param(t)
+        if len(rows) != 1 or rows[0][0] != 0 or rows[0][1] != t.shape[0]:
+            raise NotImplementedError("autodiff: a norm's affine vector is trained whole, not on row ranges")
+        return rows[0][2]
 
     def has(self, t: torch.Tensor) -> bool:
         return id(_base(t)) in self.buf
@@ -204,7 +213,12 @@ def _rule_groupnorm(B, x, gamma, beta, out, kw):
     def rule(G: Grads):
         if kw.get("reduce") is not None:
             raise NotImplementedError("autodiff: frame-sharded GroupNorm is not differentiated")
-        G.add(x, B.groupnorm_bwd(x, gamma, beta, G.view(out), rows_per_group=kw["rows_per_group"], eps=kw["eps"], silu=kw["silu"], groups=kw.get("groups", 32)))
+        aff = {}
+        if G.wants(gamma):                                   # trained affine parameters (a vector is trained whole: one row range or the tensor itself)
+            aff["dgamma"] = G.param_whole(gamma)
+        if G.wants(beta):
+            aff["dbeta"] = G.param_whole(beta)
+        G.add(x, B.groupnorm_bwd(x, gamma, beta, G.view(out), rows_per_group=kw["rows_per_group"], eps=kw["eps"], silu=kw["silu"], groups=kw.get("groups", 32), **aff))
     return rule
 
 

@@ -75,6 +75,15 @@ class GemmDwArgs(C.Structure):
     ]
 
 
+class ConvDwArgs(C.Structure):
+    """me_conv_dw_args (include/motioned_tune.h)."""
+    _fields_ = [
+        ("dY", _vp), ("X", _vp), ("dW", _vp), ("work", _vp),
+        ("M", _i32), ("N", _i32), ("K", _i32), ("lddy", _i32), ("ldx", _i32), ("dy_is_f16", _i32),
+        ("Hin", _i32), ("Win", _i32), ("Hout", _i32), ("Wout", _i32), ("stride", _i32), ("ups", _i32), ("pad0", _i32), ("alpha", _f32),
+    ]
+
+
 class RefreshDesc(C.Structure):
     """me_refresh_desc: one row range of a weight derived from trained fp32 masters (me_refresh_weights)."""
     _fields_ = [
@@ -197,6 +206,17 @@ IO_SYMBOLS = {
     "me_video_grid_u8": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
 }
 
+# every symbol include/motioned_tune.h declares (csrc/tune.hip: stage-1 tuning of the 3x3 convolutions and the GroupNorm affine parameters; outside
+# the denoising-step ABI as well)
+TUNE_SYMBOLS = {
+    "me_conv_dw": (C.c_int, [C.POINTER(ConvDwArgs), _vp]),
+    "me_conv_dw_work_bytes": (_i64, [_i32, _i32, _i32]),
+    "me_conv_dw_splits": (_i32, [_i32, _i32, _i32]),
+    "me_groupnorm_bwd_params": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _f32, _i32, _f32, _vp, _vp]),
+    "me_groupnorm_bwd_params_work_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "me_refresh_ups4": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -217,7 +237,7 @@ def lib() -> C.CDLL:
         # and every launch would then fail with hipErrorNoDevice -- so make sure torch is loaded first.
         import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS, **TUNE_SYMBOLS}.items():
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         if L.me_abi_version() != ABI_VERSION:

@@ -487,14 +487,48 @@ def unet_tune_pack(P: Packed, names: Sequence[str]) -> List[str]:
     """The packed tensors (cache keys) that hold the UNet parameters `names` in the single-branch forward as the autodiff tape records it
     (LayerNorms not folded): what util.UNetTuner trains.  Built here, in the fusions unet_forward uses -- q|k|v of attn1 / attn_temp, every
     block's attn2 k|v in the one text projection (text_kv_all), the GEGLU interleave of ff.net.0.proj.  (The motion adapter's parameters are
-    not reached by this forward -- it runs with ControlNet residuals only -- and the caller leaves them out.)  Every parameter whose packed form
-    is not a dense transformer-block projection -- 3x3 / temporal convolutions, norms (LayerNorm fold sources), the fused time_emb_proj,
-    proj_in / proj_out -- raises NotImplementedError naming it."""
+    not reached by this forward -- it runs with ControlNet residuals only -- and the caller leaves them out.)  Trained: the dense transformer-block
+    projections; the 3x3 convolutions of the residual blocks and of the down- / upsamplers, conv_shortcut, proj_in / proj_out (with their biases);
+    the GroupNorm affine parameters (resnets.*.norm1 / norm2, attentions.*.norm, conv_norm_out).  Everything else -- temporal convolutions, the fused
+    time_emb_proj, the time embedding, conv_in / conv_out, the LayerNorm affine parameters (fold sources) -- raises NotImplementedError naming it."""
     blocks = {f"{b}.transformer_blocks.0": b for b in attention_block_names(True)}
     text_kv = [f"{b}.transformer_blocks.0.attn2.{w}.weight" for b in attention_block_names(True) for w in ("to_k", "to_v")]
+    attn_blocks = set(attention_block_names(True))
     keys, bad = [], []
+
+    def plain(n: str, vector: bool) -> None:
+        if vector:
+            P.vec(n)
+            keys.append("vec:" + n)
+        else:
+            P.mat(n)
+            keys.append("mat:" + n)
+
     for n in names:
         parts = n.split(".")
+        mod, leaf = ".".join(parts[:-1]), parts[-1]
+        if leaf not in ("weight", "bias"):
+            bad.append(n)
+            continue
+        # convolutions and GroupNorms outside the transformer blocks
+        if len(parts) >= 5 and parts[-4] == "resnets" and parts[-2] in ("conv1", "conv2", "conv_shortcut"):
+            plain(n, leaf == "bias")
+            continue
+        if len(parts) >= 5 and parts[-4] == "resnets" and parts[-2] in ("norm1", "norm2"):
+            plain(n, True)
+            continue
+        if mod.endswith(("downsamplers.0.conv", "upsamplers.0.conv")) and parts[0] in ("down_blocks", "up_blocks"):
+            plain(n, leaf == "bias")
+            continue
+        if mod.rpartition(".")[0] in attn_blocks and parts[-2] in ("proj_in", "proj_out"):     # 1x1, dense
+            plain(n, leaf == "bias")
+            continue
+        if mod.rpartition(".")[0] in attn_blocks and parts[-2] == "norm":
+            plain(n, True)
+            continue
+        if mod == "conv_norm_out":
+            plain(n, True)
+            continue
         head = ".".join(parts[:5]) if parts[0] == "mid_block" else ".".join(parts[:6])
         tail = n[len(head) + 1:]
         if head not in blocks:
@@ -522,8 +556,10 @@ def unet_tune_pack(P: Packed, names: Sequence[str]) -> List[str]:
         else:
             bad.append(n)
     if bad:
-        raise NotImplementedError(f"UNet tuning trains the dense transformer-block projections (attn1, attn2, attn_temp, ff) only; {len(bad)} selected "
-                                  f"parameter(s) are not supported: {bad[:8]}")
+        raise NotImplementedError("UNet tuning trains the dense transformer-block projections (attn1, attn2, attn_temp, ff), the 3x3 convolutions (resnets.*.conv1 / conv2, "
+                                  "down- / upsamplers), conv_shortcut, proj_in / proj_out and the GroupNorm affine parameters; temporal convolutions (temp_conv*), time_emb_proj, "
+                                  "the time embedding, conv_in / conv_out and the LayerNorm affine parameters are left for a later change.  "
+                                  f"{len(bad)} selected parameter(s) are not supported: {bad[:8]}")
     return sorted(set(keys))
 
 

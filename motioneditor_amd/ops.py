@@ -686,11 +686,10 @@ def rows_to_nchw5(rows: torch.Tensor, B: int, Cc: int, f: int, h: int, w: int) -
 # Backward primitives (the kernel-level contract of motioneditor_amd/autodiff.py; SURVEY.md 8f rank 1 "null-text" and rank 4
 # "adapter training").  Their CPU statements live in tests/emu_ops.py and are pinned, through util.null_optimization /
 # util.adapter_training_grads, against the reference's own optimisation.  Every entry is a HIP kernel (csrc/bwd.hip, attn_bwd.hip,
-# train.hip) or me_gemm itself on transposed weights; torch only allocates and moves data (transposes of constant weights, fp16
+# train.hip, tune.hip) or me_gemm itself on transposed weights; torch only allocates and moves data (transposes of constant weights, fp16
 # casts of gradients) -- no torch arithmetic, no CPU fallback.  Contract: gradients are fp32 [rows, ld] views of the tape's
 # buffers; entries that take `dst` ACCUMULATE into it (+=).  Not differentiated (they raise): edited / masked attention segments,
-# shared query items, frame- / pixel-sharded row orders, the temporal editor's kv_map, 3x3-convolution weights, the pad-(0,1,0,1)
-# convolution of the VAE encoder.
+# shared query items, frame- / pixel-sharded row orders, the temporal editor's kv_map, the pad-(0,1,0,1) convolution of the VAE encoder.
 # ---------------------------------------------------------------------------------------------------------------------
 _wT_cache = {}
 
@@ -854,13 +853,23 @@ def temporal_attention_bwd(q, k, v, out, dout, *, heads, dh, batch, frames, npix
     return dq, dk, dv
 
 
-def groupnorm_bwd(x, gamma, beta, dy, *, rows_per_group, eps, silu, groups=32):
+def groupnorm_bwd(x, gamma, beta, dy, *, rows_per_group, eps, silu, groups=32, dgamma=None, dbeta=None):
+    """dx (fp32) of the GroupNorm (+ SiLU) forward; with dgamma / dbeta (fp32 [C], either may be None) the affine gradients are ACCUMULATED into them as
+    well (me_groupnorm_bwd_params: dgamma += sum_rows dz xhat, dbeta += sum_rows dz, dz = dy through the SiLU)."""
     _chk2d(x, "groupnorm_bwd.x")
     _chk_grad(dy, "groupnorm_bwd.dy")
     dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     scratch = _work(capi.lib().me_groupnorm_bwd_scratch_bytes(x.shape[0], rows_per_group, groups), x.device, "gnbwd")
     capi.check(capi.lib().me_groupnorm_bwd(dx.data_ptr(), dx.stride(0), x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(), dy.data_ptr(), dy.stride(0),
                                            x.shape[0], rows_per_group, x.shape[1], groups, eps, 1 if silu else 0, scratch.data_ptr(), _stream()), "me_groupnorm_bwd")
+    if dgamma is not None or dbeta is not None:
+        for t in (dgamma, dbeta):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.shape[1]):
+                raise ValueError(f"groupnorm_bwd: dgamma / dbeta must be contiguous fp32 [{x.shape[1]}] tensors")
+        work = _work(capi.lib().me_groupnorm_bwd_params_work_bytes(x.shape[0], rows_per_group, x.shape[1], groups), x.device, "gnp")
+        capi.check(capi.lib().me_groupnorm_bwd_params(_p(dgamma), _p(dbeta), x.data_ptr(), x.stride(0), gamma.data_ptr(), beta.data_ptr(), dy.data_ptr(), dy.stride(0),
+                                                      x.shape[0], rows_per_group, x.shape[1], groups, eps, 1 if silu else 0, 1.0, work.data_ptr(), _stream()),
+                   "me_groupnorm_bwd_params")
     return dx
 
 
@@ -902,10 +911,11 @@ def scratch_trim() -> int:
 
 
 def gemm_dw(dy, x, *, dst, taps, K, M, alpha=1.0, conv=None, tconv=None):
-    """dst (fp32 [N, taps, K]) += dW of me_gemm's y = alpha * gather(x) @ w^T for dense and TemporalConv layers (the adapter has no 3x3
-    convolution): the token axis is the MFMA contraction, per-split fp32 partial tiles are folded in a fixed order."""
+    """dst (fp32 [N, taps, K]) += dW of me_gemm's y = alpha * gather(x) @ w^T: the token axis is the MFMA contraction, per-split fp32 partial tiles are
+    folded in a fixed order.  Dense and TemporalConv layers: me_gemm_dw, one launch per tap.  conv=(Hin, Win, Hout, Wout, stride, ups[, pad0]), the 3x3
+    convolutions (stride 1 / 2, nearest-2x upsampled): me_conv_dw, all nine taps in ONE launch."""
     if conv is not None:
-        raise NotImplementedError("gemm_dw: 3x3 convolution weights are not trained (the adapter has none)")
+        return _conv_dw(dy, x, dst=dst, taps=taps, K=K, M=M, alpha=alpha, conv=conv)
     if tconv is not None and len(tconv) > 3:
         raise NotImplementedError("gemm_dw: the frame-sharded TemporalConv is not differentiated")
     N = dy.shape[1]
@@ -924,6 +934,24 @@ def gemm_dw(dy, x, *, dst, taps, K, M, alpha=1.0, conv=None, tconv=None):
     for tap in range(taps):
         a.tap = tap
         capi.check(capi.lib().me_gemm_dw(C.byref(a), _stream()), "me_gemm_dw")
+    return dst
+
+
+def _conv_dw(dy, x, *, dst, taps, K, M, alpha, conv):
+    N = dy.shape[1]
+    if taps != 9 or dst.dtype != torch.float32 or not dst.is_contiguous() or tuple(dst.shape) != (N, 9, K):
+        raise ValueError(f"gemm_dw: the dst of a 3x3 convolution must be a contiguous fp32 [{N}, 9, {K}] tensor")
+    _chk2d(x, "gemm_dw.x")
+    a = capi.ConvDwArgs()
+    a.dY, a.X, a.dW = dy.data_ptr(), x.data_ptr(), dst.data_ptr()
+    a.M, a.N, a.K, a.lddy, a.ldx, a.dy_is_f16 = M, N, K, dy.stride(0), x.stride(0), 1 if dy.dtype == F16 else 0
+    a.Hin, a.Win, a.Hout, a.Wout, a.stride, a.ups = conv[:6]
+    a.pad0 = 1 if len(conv) > 6 and conv[6] else 0
+    a.alpha = alpha
+    if dy.shape[0] < M or (a.Hout > 0 and a.Wout > 0 and x.shape[0] < (M // (a.Hout * a.Wout)) * a.Hin * a.Win):
+        raise ValueError("gemm_dw: dy / x hold fewer rows than the convolution's geometry reads")
+    a.work = _work(capi.lib().me_conv_dw_work_bytes(M, N, K), dy.device, "convdw").data_ptr()
+    capi.check(capi.lib().me_conv_dw(C.byref(a), _stream()), "me_conv_dw")
     return dst
 
 
@@ -1000,15 +1028,28 @@ def mse_seed(eps_u: torch.Tensor, target: torch.Tensor, *, eps_c: Optional[torch
 class RefreshTable:
     """A device-resident me_refresh_desc table (refresh_table) and the tensors its pointers name, kept alive with it."""
 
-    def __init__(self, buf: torch.Tensor, n: int, total_rows: int, keep):
+    def __init__(self, buf: Optional[torch.Tensor], n: int, total_rows: int, keep, ups4=()):
         self.buf, self.n, self.total_rows, self.keep = buf, n, total_rows, keep
+        self.ups4 = list(ups4)   # (master fp32 [N, 9, K], dst fp16 [N, 16, K]): folded upsampler weights, one me_refresh_ups4 launch each
 
 
 def refresh_table(entries) -> RefreshTable:
     """entries: (master fp32 [rows, ld] view, dst fp16 [rows, ld] view, gamma, beta, bias, colsum, cvec) -- the last five None for a plain entry
     (dst = f16(master)); with gamma (fp32 [K]), beta (fp32 [K]), colsum / cvec (fp32 [rows] views) and an optional bias (fp32 [rows]) a LayerNorm-fold
     entry (dst = f16(master * gamma), colsum = row sums of dst, cvec = master beta + bias).  Columns: the first K = master.shape[1] of each row.
+    An entry whose master is the 3-D fp32 [N, 9, K] packing of a 3x3 convolution and whose dst is fp16 [N, 16, K] (the other five None) is the folded
+    upsampler weight of that convolution (weights.Packed.fold_ups; me_refresh_ups4).
     Validated here, then copied to the device once: me_refresh_weights reads it on every launch."""
+    if not entries:
+        raise ValueError("refresh_table: no entries")
+    ups4 = [e for e in entries if e[0].dim() == 3]
+    entries = [e for e in entries if e[0].dim() != 3]
+    for m, d, *rest in ups4:
+        if (m.dtype != torch.float32 or d.dtype != F16 or d.dim() != 3 or m.shape[1] != 9 or tuple(d.shape) != (m.shape[0], 16, m.shape[2]) or not m.is_contiguous()
+                or not d.is_contiguous() or m.shape[2] % 4 or (m.data_ptr() & 15) or (d.data_ptr() & 7) or not m.is_cuda or m.device != d.device or any(t is not None for t in rest)):
+            raise ValueError("refresh_table: a folded-upsampler entry is (master fp32 [N, 9, K], dst fp16 [N, 16, K]), contiguous, K a multiple of 4, on one device")
+    if not entries:
+        return RefreshTable(None, 0, 0, [t for e in ups4 for t in e[:2]], [(e[0], e[1]) for e in ups4])
     descs = (capi.RefreshDesc * len(entries))()
     row0 = 0
     keep = []
@@ -1029,13 +1070,15 @@ def refresh_table(entries) -> RefreshTable:
         e.row0, e.rows, e.K, e.ld_master, e.ld_dst = row0, rows, K, m.stride(0), d.stride(0)
         row0 += rows
         keep.extend(t for t in (m, d, gamma, beta, bias, colsum, cvec) if t is not None)
-    if not entries:
-        raise ValueError("refresh_table: no entries")
     host = torch.frombuffer(bytearray(C.string_at(C.addressof(descs), C.sizeof(descs))), dtype=torch.uint8)
     dev = entries[0][0].device
-    return RefreshTable(host.to(dev), len(entries), row0, keep)
+    return RefreshTable(host.to(dev), len(entries), row0, keep, [(e[0], e[1]) for e in ups4])
 
 
 def refresh_weights(table: RefreshTable) -> None:
-    """Every row of the table's entries refreshed from its fp32 master, in place, in ONE launch (me_refresh_weights)."""
-    capi.check(capi.lib().me_refresh_weights(table.buf.data_ptr(), table.n, table.total_rows, _stream()), "me_refresh_weights")
+    """Every row of the table's entries refreshed from its fp32 master, in place, in ONE launch (me_refresh_weights); every folded upsampler weight of
+    the table in one launch of its own (me_refresh_ups4)."""
+    if table.n:
+        capi.check(capi.lib().me_refresh_weights(table.buf.data_ptr(), table.n, table.total_rows, _stream()), "me_refresh_weights")
+    for m, d in table.ups4:
+        capi.check(capi.lib().me_refresh_ups4(d.data_ptr(), m.data_ptr(), m.shape[0], m.shape[2], _stream()), "me_refresh_ups4")

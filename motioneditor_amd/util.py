@@ -280,8 +280,9 @@ class AdapterTrainer:
 # ---------------------------------------------------------------------------------------------------------------------
 class UNetTuner:
     """One optimisation step of train_bg.py (stage 1) on the device: the parameters that train_bg.py's module / parameter filter selects
-    (default: attn1.to_q, attn2.to_q and attn_temp of every transformer block) are trained on the plain UNet forward (no ControlNet residuals,
-    sparse-causal attn1) against mse(model_pred, target), with clip_grad_norm_(max_grad_norm) and AdamW (the reference's defaults: lr 3e-5,
+    (default: attn1.to_q, attn2.to_q and attn_temp of every transformer block; also accepted: the 3x3 convolutions of the residual blocks and of
+    the down- / upsamplers, conv_shortcut, proj_in / proj_out and the GroupNorm affine parameters -- graph.unet_tune_pack names what is not) are
+    trained on the plain UNet forward (no ControlNet residuals, sparse-causal attn1) against mse(model_pred, target), with clip_grad_norm_(max_grad_norm) and AdamW (the reference's defaults: lr 3e-5,
     betas (0.9, 0.999), weight decay 1e-2, eps 1e-8).
 
     The gradient bucket holds exactly the selected parameters the forward REACHES: the filter also matches the motion adapter's attn_temp,
@@ -290,8 +291,8 @@ class UNetTuner:
     ranges of the packed tensors that hold them (q of a fused q|k|v; k|v stay frozen and get no weight-gradient launch).
 
     Every weight derived from a trained parameter -- the fp16 packed tensors and the LayerNorm folds (W diag(gamma), colsum, W beta + b) of
-    the inference forward -- is rewritten IN PLACE after each update by one me_refresh_weights launch, so that recorded plans and captured
-    graphs replay with the tuned weights; a derived tensor first built after tuning started is built from the live fp32 masters
+    the inference forward, the folded upsampler weights (me_refresh_ups4) -- is rewritten IN PLACE after each update by one me_refresh_weights
+    launch, so that recorded plans and captured graphs replay with the tuned weights; a derived tensor first built after tuning started is built from the live fp32 masters
     (weights.Packed.live).  No gradient, master or optimiser moment visits the host.  `save_checkpoint(dir)` writes what stage 2 and
     inference read back (checkpoint.load_unet_state_dict(resume_from_checkpoint=dir))."""
 
@@ -357,14 +358,20 @@ class UNetTuner:
 
     # -- layouts ---------------------------------------------------------------------------------------------------------------------
     def _reference_layout(self, n: str, t: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The master of `n` (or `t`, a tensor in the same packed layout) in the reference's own layout (Linear [N, K] or a vector)."""
+        """The master of `n` (or `t`, a tensor in the same packed layout) in the reference's own layout, the shape P.raw(n) has: Linear [N, K],
+        Conv2d [N, K, 3, 3] / [N, K, 1, 1] (packed tap-major as [N, 9, K] / [N, 1, K]) or a vector."""
         t, kind = (self.masters[n] if t is None else t), self.kind[n]
         if kind in ("geglu", "gegluv"):
             from .weights import Packed
             inv = torch.empty(t.shape[0], dtype=torch.long)
             inv[Packed._geglu_perm(t.shape[0] // 2)] = torch.arange(t.shape[0])
             t = t[inv.to(t.device)]
-        return t[:, 0, :] if t.dim() == 3 else t.reshape(-1)
+        if t.dim() != 3:
+            return t.reshape(-1)
+        shp = tuple(self.unet.P.state[self.unet.P.prefix + n].shape)      # from the state: never a live master's host copy
+        if len(shp) == 4:                                                # [N, kh kw, K] -> [N, K, kh, kw]
+            return t.reshape(shp[0], shp[2], shp[3], shp[1]).permute(0, 3, 1, 2)
+        return t[:, 0, :]
 
     def _const(self, key: str, make) -> torch.Tensor:
         c = self._consts.get(key)
@@ -381,7 +388,11 @@ class UNetTuner:
         for key, t in list(P.cache.items()):
             kind, _, joined = key.partition(":")
             ns = joined.split("|")
-            if kind not in ("mat", "vec", "fused", "fvec", "geglu", "gegluv", "lnw", "lnwg") or trained.isdisjoint(ns):
+            if kind not in ("mat", "vec", "fused", "fvec", "geglu", "gegluv", "lnw", "lnwg", "ups4") or trained.isdisjoint(ns):
+                continue
+            if kind == "ups4":     # the folded form of a trained upsampler convolution: rewritten from the [N, 9, K] master by me_refresh_ups4
+                sig.append((key, t.data_ptr()))
+                ents.append((self.masters[ns[0]], t, None, None, None, None, None))
                 continue
             if kind in ("lnw", "lnwg"):
                 wq, colsum, cvec = t
@@ -469,14 +480,14 @@ class UNetTuner:
         loss, ls, G = _unet_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, None, None, target, lambda: self.trainable,
                                      param_buffers=self.param_buffers)
         del G
-        out = {n: self._reference_layout(n, self.param_buffers[n] / ls).cpu() for n in self.names}
+        out = {n: self._reference_layout(n, self.param_buffers[n] / ls).cpu().contiguous() for n in self.names}
         self.grad.zero_()
         return loss, out
 
     # -- export --------------------------------------------------------------------------------------------------------------------------
     def export_state_dict(self):
         """{reference parameter name: fp32 host tensor in the reference layout} of the trained parameters."""
-        return {n: self._reference_layout(n).detach().cpu().clone() for n in self.names}
+        return {n: self._reference_layout(n).detach().cpu().contiguous().clone() for n in self.names}
 
     def save_checkpoint(self, directory) -> str:
         """`directory`/model.safetensors: the full UNet state in the reference key schema, trained parameters at their current values (the model

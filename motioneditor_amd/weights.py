@@ -142,13 +142,17 @@ class Packed:
     def mat_ups(self, name: str) -> Optional[torch.Tensor]:
         """The folded [N, 16, K] weight of the convolution behind a nearest-2x upsample (me_gemm gather mode ups = 3): the taps summed in fp32,
         rounded to the store's dtype ONCE; packed once under its own key (`update` drops it with every other tensor built from `name`).
-        None -- the caller keeps the 9-tap form -- while a trainer rewrites this parameter's packed tensor in place (`live`, `rehome`): the in-place
-        refresh knows the plain packings and the LayerNorm folds only, a folded copy would go stale behind it."""
+        While a trainer rewrites this parameter's packed tensor in place, no NEW folded copy is built: the caller keeps the 9-tap form (None).  A fold
+        that already exists when the background tuner takes the parameter over (`live`) stays -- recorded plans hold its address -- and keeps being
+        handed out: the tuner rewrites it in place with every step (me_refresh_ups4).  AdapterTrainer's `rehome` knows the plain packings only: there
+        the folded copy is dropped, it would go stale."""
         # (only the plain `mat:` packing of a convolution is ever rehomed -- AdapterTrainer rehomes adapter_pack's keys, and a 3x3 weight has no other
         #  packing -- so the exact key is the whole test; a new packing kind of convolution weights would have to be named here)
-        if name in self.live or ("mat:" + name) in self._rehomed:
+        if ("mat:" + name) in self._rehomed:
             self.cache.pop("ups4:" + name, None)
             return None
+        if name in self.live:
+            return self.cache.get("ups4:" + name)
         key = "ups4:" + name
         hit = self.cache.get(key)
         return hit if hit is not None else self._put(key, self.fold_ups(self.raw(name)))

@@ -244,9 +244,10 @@ typedef struct me_tattn_args {
   void* O;
   int32_t ldq, ldk, ldv, ldo;
   int32_t heads, dh;
-  int32_t batch, frames, npix; /* dh 40 / 80 / 160: any frames (of K/V) <= 64, the MFMA form ("tattn_mfma_kernel<dh,32|64>").  Every other dh that
-                                  divides 320 (and frames > 64): the per-thread form ("tattn_kernel<frames>"), frames in {8,16,24,32,40,48} and
-                                  (320 / dh) * query frames <= 512 -- one thread per (head of a 320-column slice, query frame) */
+  int32_t batch, frames, npix; /* dh 40 / 80 / 160: any frames (of K/V) <= 64, the MFMA form ("tattn_mfma_kernel<dh,32|64>"); 64 < frames <= 256, the
+                                  key-tiled form ("tattn_long_kernel<dh>": 64 query frames per block, keys in stages of 64 under an online softmax);
+                                  frames > 256: ME_EINVAL.  Every other dh that divides 320: the per-thread form ("tattn_kernel<frames>"), frames in
+                                  {8,16,24,32,40,48} and (320 / dh) * query frames <= 512 -- one thread per (head of a 320-column slice, query frame) */
   int32_t kv_map[8];           /* batch <= 8 */
   float scale;
   /* frame sharding: Q/O hold q_frames local frames starting at global frame q_frame0 (0, 0 = all frames);

@@ -277,6 +277,202 @@ __global__ __launch_bounds__(64 * (SLICE / DH)) void tattn_mfma_kernel(const me_
   });
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The key-tiled form (dh 40 / 80 / 160, 64 < frames <= 256).  The MFMA form above holds ALL keys of a (pixel, slice) in LDS
+// (84 KB at 64 frames); here a block owns 64 QUERY frames of one (batch entry, pixel, slice) and walks the keys in stages
+// of 64, frame 0 up to the stage that holds its last query's diagonal (stages wholly above it are never read).  Every stage
+// is staged and multiplied exactly as tattn_mfma_kernel<DH,64> does; between stages a running maximum and a running sum per
+// query (fp32) carry the softmax, and the O^T accumulators stay in registers, rescaled by exp2(m_old - m_new).
+// Every query -- the pad queries beyond q_frames too -- sees key frame 0 in stage 0, so m is finite after the first stage
+// and the -1.0e30 sentinel only ever meets a finite maximum.  Blocks are numbered with the query block fastest: block qb
+// re-reads the K/V rows blocks 0..qb-1 staged, (nqb + 1) / 2 reads of K/V in all, and its neighbours have just pulled them
+// into L2.  No atomics; the stage order is fixed, so two calls are bitwise equal.
+constexpr int LONG_MAX_FRAMES = 256;
+
+template <int DH>
+__global__ __launch_bounds__(64 * (SLICE / DH)) void tattn_long_kernel(const me_tattn_args a) {
+  constexpr int KP = 64, HPS = SLICE / DH, NTHR = 64 * HPS;
+  constexpr int D32 = (DH + 31) / 32, DT = (DH + 15) / 16, NT = KP / 16, KK = KP / 32;
+  constexpr int SLDB = SLD * 2;
+  __shared__ __attribute__((aligned(16))) char smem[2 * KP * SLDB + 128];
+  char* sK = smem;
+  char* sV = smem + KP * SLDB;
+
+  const int F = a.frames;
+  const int nslice = (a.heads * a.dh) / SLICE;
+  const int QF = a.q_frames > 0 ? a.q_frames : F;
+  const int q0 = a.q_frames > 0 ? a.q_frame0 : 0;
+  const int nqb = (QF + KP - 1) / KP;
+  int bid = blockIdx.x;
+  const int qb = bid % nqb;               // query blocks of one (batch entry, pixel, slice) are neighbours
+  bid /= nqb;
+  const int sl = bid % nslice;
+  bid /= nslice;
+  const int p = bid % a.npix;
+  const int b = bid / a.npix;
+  const int kb = a.kv_map[b];
+  const int parts = a.kv_parts > 1 ? a.kv_parts : 1;
+  const int fpp = F / parts;
+  const int tid = threadIdx.x, lane = tid & 63, hl = tid >> 6, g = lane >> 4, l15 = lane & 15;
+  const f16* __restrict__ Q = reinterpret_cast<const f16*>(a.Q);
+  const f16* __restrict__ K = reinterpret_cast<const f16*>(a.K);
+  const f16* __restrict__ V = reinterpret_cast<const f16*>(a.V);
+  f16* __restrict__ O = reinterpret_cast<f16*>(a.O);
+  const int col0 = sl * SLICE, lcol = hl * DH;
+  const int il0 = qb * KP;                                        // first local query frame of this block
+  const int last = q0 + (il0 + KP - 1 < QF ? il0 + KP - 1 : QF - 1);   // global frame of the last real query: < F
+  const int nstage = last / KP + 1;
+
+  if (tid < 8) reinterpret_cast<uint4*>(smem + 2 * KP * SLDB)[tid] = make_uint4(0u, 0u, 0u, 0u);   // slack behind the last row
+
+  // Q fragments (operand B), read once: lane (q = l15, g) holds Q[frame il0 + qt*16 + l15][ks*32 + g*8 .. +8], zero beyond dh / QF
+  f16x8 fq[NT][D32];
+  long qrow[NT];
+#pragma unroll
+  for (int qt = 0; qt < NT; ++qt) {
+    const int il = il0 + qt * 16 + l15, i = q0 + il;
+    qrow[qt] = il < QF ? (a.q_parts > 1 ? ((long)(i / fpp) * a.batch + b) * fpp * a.npix + (long)(i % fpp) * a.npix + p : ((long)b * QF + il) * a.npix + p) : -1;
+#pragma unroll
+    for (int ks = 0; ks < D32; ++ks) {
+      const int d = ks * 32 + g * 8;
+      U128 u;
+      u.u = (qrow[qt] >= 0 && d < DH) ? ldg128(Q + qrow[qt] * a.ldq + col0 + lcol + d) : make_uint4(0u, 0u, 0u, 0u);
+      fq[qt][ks] = u.h;
+    }
+  }
+
+  const float c = a.scale * 1.4426950408889634f;
+  float m[NT], l[NT];                                             // running maximum (all lanes of a query agree), running sum (this lane's keys)
+  f32x4 o[DT][NT];
+#pragma unroll
+  for (int qt = 0; qt < NT; ++qt) {
+    m[qt] = -1.0e30f;
+    l[qt] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o[dt][qt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const unsigned vlane = (unsigned)(size_t)(sV + (g * 4 + (l15 >> 2)) * SLDB + (l15 & 3) * 8 + lcol * 2);
+
+  for (int st = 0; st < nstage; ++st) {
+    const int k0 = st * KP;
+    if (st) __syncthreads();                                      // every wave is done with the previous stage's tiles
+    // stage K and V rows k0 .. k0+63: 41 chunks (40 real + the pad chunk, zeroed); rows >= F are zero
+    for (int idx = tid; idx < KP * (SLD / 8); idx += NTHR) {
+      const int jj = idx / (SLD / 8), cc = idx - jj * (SLD / 8), j = k0 + jj;
+      uint4 kq = make_uint4(0u, 0u, 0u, 0u), vq = kq;
+      if (j < F && cc < SLICE / 8) {
+        const long row = ((long)(j / fpp) * a.batch + kb) * fpp * a.npix + (long)(j % fpp) * a.npix + p;
+        kq = ldg128(K + row * a.ldk + col0 + cc * 8);
+        vq = ldg128(V + row * a.ldv + col0 + cc * 8);
+      }
+      *reinterpret_cast<uint4*>(sK + jj * SLDB + cc * 16) = kq;
+      *reinterpret_cast<uint4*>(sV + jj * SLDB + cc * 16) = vq;
+    }
+    __syncthreads();
+
+    // S^T[key tile kt][query tile qt] of this stage
+    f32x4 s[NT][NT];
+#pragma unroll
+    for (int qt = 0; qt < NT; ++qt)
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt) s[qt][kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < D32; ++ks)
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt) {
+        const f16x8 fk = *reinterpret_cast<const f16x8*>(sK + (kt * 16 + l15) * SLDB + (lcol + ks * 32 + g * 8) * 2);
+#pragma unroll
+        for (int qt = 0; qt < NT; ++qt) s[qt][kt] = mfma16(fk, fq[qt][ks], s[qt][kt]);
+      }
+
+    // online causal softmax per query (= per lane column; the 4 lane groups g hold different keys of it)
+    f16x8 pf[NT][KK];
+#pragma unroll
+    for (int qt = 0; qt < NT; ++qt) {
+      const int i = q0 + il0 + qt * 16 + l15;
+      float mx = -1.0e30f;
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s[qt][kt][r] = (k0 + kt * 16 + g * 4 + r <= i) ? s[qt][kt][r] * c : -1.0e30f;
+          mx = fmaxf(mx, s[qt][kt][r]);
+        }
+      mx = fmaxf(m[qt], xor32_max(xor16_max(mx)));                // finite from stage 0 on: key frame 0 is below every diagonal
+      const float alpha = __builtin_amdgcn_exp2f(m[qt] - mx);     // stage 0: exp2(-1e30 - finite) = 0 on zero accumulators
+      m[qt] = mx;
+      float ls = 0.f;
+#pragma unroll
+      for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s[qt][kt][r] = __builtin_amdgcn_exp2f(s[qt][kt][r] - mx);
+          ls += s[qt][kt][r];
+        }
+      l[qt] = l[qt] * alpha + ls;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) o[dt][qt] *= alpha;
+#pragma unroll
+      for (int kk = 0; kk < KK; ++kk) {   // operand B k-slot (g, j) = key kk*32 + (j>>2)*16 + g*4 + (j&3)
+        union { f16x2 h[4]; f16x8 v; } f;
+#pragma unroll
+        for (int h2 = 0; h2 < 2; ++h2) {
+          f.h[h2] = __builtin_convertvector((f32x2){s[qt][2 * kk][2 * h2], s[qt][2 * kk][2 * h2 + 1]}, f16x2);
+          f.h[2 + h2] = __builtin_convertvector((f32x2){s[qt][2 * kk + 1][2 * h2], s[qt][2 * kk + 1][2 * h2 + 1]}, f16x2);
+        }
+        pf[qt][kk] = f.v;
+      }
+    }
+
+    // O^T[d tile dt][query tile qt] += V^T P^T (the transposed read as in tattn_mfma_kernel)
+    t_static_for(std::make_integer_sequence<int, DT>{}, [&](auto dt_c) {
+      constexpr int dt = decltype(dt_c)::value;
+      t_static_for(std::make_integer_sequence<int, KK>{}, [&](auto kk_c) {
+        constexpr int kk = decltype(kk_c)::value;
+        union { uint2 u[2]; f16x8 v; } fv;
+        fv.u[0] = t_lds_tr16<(kk * 32) * SLDB + dt * 32>(vlane);
+        fv.u[1] = t_lds_tr16<(kk * 32 + 16) * SLDB + dt * 32>(vlane);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fv.u[0]), "+v"(fv.u[1]));
+#pragma unroll
+        for (int qt = 0; qt < NT; ++qt) o[dt][qt] = mfma16(fv.v, pf[qt][kk], o[dt][qt]);
+      });
+    });
+  }
+
+  float linv[NT];
+#pragma unroll
+  for (int qt = 0; qt < NT; ++qt) linv[qt] = 1.0f / xor32_sum(xor16_sum(l[qt]));
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    const int d = dt * 16 + g * 4;
+    if (d < DH) {
+#pragma unroll
+      for (int qt = 0; qt < NT; ++qt) {
+        if (qrow[qt] < 0) continue;
+        U64 ov;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ov.e[r] = (f16)(o[dt][qt][r] * linv[qt]);
+        *reinterpret_cast<uint2*>(O + qrow[qt] * a.ldo + col0 + lcol + d) = ov.u;
+      }
+    }
+  }
+}
+
+template <int DH>
+int launch_tattn_long(const me_tattn_args* a, hipStream_t st) {
+  const int nslice = (a->heads * a->dh) / SLICE;
+  const int QF = a->q_frames > 0 ? a->q_frames : a->frames;
+  const long blocks = (long)a->batch * a->npix * nslice * ((QF + 63) / 64);
+  (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
+  hipLaunchKernelGGL((tattn_long_kernel<DH>), dim3((unsigned)blocks), dim3(64 * (SLICE / DH)), 0, st, *a);
+  {
+    char nm[64];
+    snprintf(nm, sizeof(nm), "tattn_long_kernel<%d>", DH);
+    me_set_kernel(nm);
+  }
+  return hipGetLastError() == hipSuccess ? ME_OK : ME_EHIP;
+}
+
 template <int DH, int KP>
 int launch_tattn_mfma(const me_tattn_args* a, hipStream_t st) {
   const int nslice = (a->heads * a->dh) / SLICE;
@@ -339,6 +535,17 @@ extern "C" int me_tattn(const me_tattn_args* a, void* stream) {
       case 40: rc = big ? launch_tattn_mfma<40, 64>(a, st) : launch_tattn_mfma<40, 32>(a, st); break;
       case 80: rc = big ? launch_tattn_mfma<80, 64>(a, st) : launch_tattn_mfma<80, 32>(a, st); break;
       default: rc = big ? launch_tattn_mfma<160, 64>(a, st) : launch_tattn_mfma<160, 32>(a, st); break;
+    }
+    if (rc != ME_OK) me_set_error("me_tattn: kernel launch failed");
+    return rc;
+  }
+  // longer clips: the key-tiled kernel, whatever ME_TATTN_MFMA says (that switch chooses between the two forms of frames <= 64)
+  if (a->frames > 64 && a->ldo % 4 == 0 && (a->dh == 40 || a->dh == 80 || a->dh == 160)) {
+    if (a->frames > LONG_MAX_FRAMES) { me_set_error("me_tattn: frames must be <= 256 (the limit of the key-tiled kernel tattn_long_kernel)"); return ME_EINVAL; }
+    switch (a->dh) {
+      case 40: rc = launch_tattn_long<40>(a, st); break;
+      case 80: rc = launch_tattn_long<80>(a, st); break;
+      default: rc = launch_tattn_long<160>(a, st); break;
     }
     if (rc != ME_OK) me_set_error("me_tattn: kernel launch failed");
     return rc;

@@ -328,7 +328,9 @@ def temporal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, hea
                        kv_parts: int = 1, q_parts: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """frames = K/V frames.  Frame-sharded: q holds q_frames local frames from global frame q_frame0; k, v are the
     all-gather (part-major) of kv_parts equal frame shards.  Pixel-sharded (after the frame<->pixel all-to-all): q, k, v and
-    the output all hold every frame of this rank's npix pixels, part-major (q_parts == kv_parts)."""
+    the output all hold every frame of this rank's npix pixels, part-major (q_parts == kv_parts).
+    dh 40 / 80 / 160 take up to 256 frames (above 64 the key-tiled kernel, csrc/tattn.hip tattn_long_kernel); other head sizes
+    8, 16, ... 48."""
     for t, n in ((q, "q"), (k, "k"), (v, "v")):
         _chk2d(t, "temporal_attention." + n)
     if out is None:

@@ -217,6 +217,13 @@ TUNE_SYMBOLS = {
     "me_refresh_ups4": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
 }
 
+# every symbol include/motioned_long.h declares (csrc/tattn_bwd_long.hip: the temporal-attention backward on clips of 65 .. 256 frames; outside the
+# denoising-step ABI as well)
+LONG_SYMBOLS = {
+    "me_tattn_bwd_long": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, C.c_float, _vp, _i64, _vp]),
+    "me_tattn_bwd_long_work_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+}
+
 _lib = None
 
 
@@ -237,7 +244,7 @@ def lib() -> C.CDLL:
         # and every launch would then fail with hipErrorNoDevice -- so make sure torch is loaded first.
         import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS, **TUNE_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS, **TUNE_SYMBOLS, **LONG_SYMBOLS}.items():
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         if L.me_abi_version() != ABI_VERSION:

@@ -849,6 +849,14 @@ def temporal_attention_bwd(q, k, v, out, dout, *, heads, dh, batch, frames, npix
     _chk_grad(dout, "temporal_attention_bwd.dout")
     rows, C_ = batch * frames * npix, heads * dh
     dq, dk, dv = (torch.empty((rows, C_), dtype=torch.float32, device=q.device) for _ in range(3))
+    if frames > 64:   # the key-tiled kernels (include/motioned_long.h): softmax statistics rebuilt into a scratch of two fp32 per (row, head)
+        L = capi.lib()
+        nbytes = L.me_tattn_bwd_long_work_bytes(batch, frames, npix, heads)
+        work = _work(nbytes, q.device, "tbwdlong")
+        capi.check(L.me_tattn_bwd_long(dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), q.data_ptr(), q.stride(0),
+                                       k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), dout.data_ptr(), dout.stride(0), batch, frames, npix, heads, dh,
+                                       dh ** -0.5 if scale is None else scale, work.data_ptr(), nbytes, _stream()), "me_tattn_bwd_long")
+        return dq, dk, dv
     capi.check(capi.lib().me_tattn_bwd(dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), q.data_ptr(), q.stride(0),
                                        k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), dout.data_ptr(), dout.stride(0), batch, frames, npix, heads, dh,
                                        dh ** -0.5 if scale is None else scale, _stream()), "me_tattn_bwd")

@@ -7,7 +7,9 @@ tensors in place of the dataset, CLIP and the checkpoints (none exist offline):
     model_pred = unet(noisy, t, ehs, down_block_additional_residuals, mid_block_additional_residual).sample      (:364)
     loss = mse(model_pred, noise); backward; clip_grad_norm_(1.0); AdamW.step()  -- only controlnet_adapter.* trains (:365-384)
 
-    python examples/train_adapter.py [--frames 8 --size 128 --steps 2] [--prompt "a girl is dancing" [--checkpoint SD15_DIR]]
+    python examples/train_adapter.py [--frames 8 --size 128 --steps 2] [--prompt "a girl is dancing" [--checkpoint SD15_DIR]] [--gradient-checkpointing]
+--gradient-checkpointing: `unet.enable_gradient_checkpointing()` (the reference's `gradient_checkpointing: True`): same losses and updates bit for bit,
+a fraction of the activation memory, one more forward of the differentiated blocks per step -- what clips past 96 frames at 512 x 512 need on one card.
 --prompt: `ehs = text_encoder(prompt_ids)[0]` (train_adaptor.py:339) with the native CLIP classes instead of a synthetic embedding.
 --video-dir DIR [--mask-dir man.mask --condition openposefull --suffix .png]: pixel_values and the source skeleton come from data.dataset.VideoDataset
 (train_adaptor.py:325, :348) instead of synthetic tensors; --frames and --size are its n_sample_frames and width / height.
@@ -86,6 +88,8 @@ def main() -> None:
     ap.add_argument("--lr", type=float, default=3e-5)
     ap.add_argument("--prompt", default=None, help="encode this prompt with the native CLIP text encoder instead of a synthetic embedding")
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
+    ap.add_argument("--gradient-checkpointing", action="store_true",
+                    help="unet.enable_gradient_checkpointing(), the reference's default: keep block boundaries only, recompute the blocks in the backward (long clips)")
     sys.path.insert(0, str(ROOT / "examples"))
     from run_edit import add_clip_arguments
     add_clip_arguments(ap)
@@ -96,6 +100,8 @@ def main() -> None:
     from motioneditor_amd.models.vae import AutoencoderKL
     dev = "cuda"
     vae, unet, cn = AutoencoderKL.from_synthetic(dev), UNet2DConditionModel.from_synthetic(dev), ControlNetModel.from_synthetic(dev)
+    if args.gradient_checkpointing:
+        unet.enable_gradient_checkpointing()                                                                       # (train_adaptor.py:182-183)
     trainer = util.AdapterTrainer(unet, lr=args.lr)
     ehs = encode_prompt(args.prompt, args.checkpoint, dev) if args.prompt is not None else None
     import time

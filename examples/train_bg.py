@@ -59,6 +59,8 @@ def main() -> None:
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
     ap.add_argument("--trainable-modules", nargs="+", default=["attn1.to_q", "attn2.to_q", "attn_temp"], metavar="M",
                     help="train_bg.py's trainable_modules: every parameter under a module whose path ends with one of these is trained")
+    ap.add_argument("--gradient-checkpointing", action="store_true",
+                    help="unet.enable_gradient_checkpointing(), the reference's default: keep block boundaries only, recompute the blocks in the backward (long clips)")
     add_clip_arguments(ap)
     args = ap.parse_args()
     from motioneditor_amd import util
@@ -66,6 +68,8 @@ def main() -> None:
     from motioneditor_amd.models.vae import AutoencoderKL
     dev = "cuda"
     vae, unet = AutoencoderKL.from_synthetic(dev), UNet2DConditionModel.from_synthetic(dev)
+    if args.gradient_checkpointing:
+        unet.enable_gradient_checkpointing()                                                                       # (train_bg.py:182-183)
     tuner = util.UNetTuner(unet, trainable_modules=tuple(args.trainable_modules), lr=args.lr)
     print(f"training {len(tuner.names)} parameters ({tuner.master.numel() / 1e6:.1f} M values); {len(tuner.unreached)} selected parameters of the "
           "adapter are not reached by this forward and stay frozen")

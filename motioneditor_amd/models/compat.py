@@ -33,7 +33,17 @@ class ModuleShims:
     def enable_xformers_memory_efficient_attention(self, *a, **k):   # inference.py:164-168: attention is always the fused me_attn kernel
         return self
 
-    def enable_gradient_checkpointing(self):                     # inference.py:170-171 (training-time memory knob; the tape recomputes GEGLU only)
+    gradient_checkpointing = False
+
+    def enable_gradient_checkpointing(self):
+        """inference.py:170-171, train_adaptor.py / train_bg.py (`gradient_checkpointing: True`): the default of `gradient_checkpointing=` in
+        util.null_optimization, util.adapter_training_grads / AdapterTrainer and util.UNetTuner -- the autodiff tape then keeps the boundary tensors of
+        each resnet / transformer / adapter block only and runs the block again in the backward walk."""
+        self.gradient_checkpointing = True
+        return self
+
+    def disable_gradient_checkpointing(self):
+        self.gradient_checkpointing = False
         return self
 
     # -- device / dtype

@@ -10,6 +10,7 @@ are the same buffer.
 from __future__ import annotations
 
 import contextlib
+import functools
 from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence
 
@@ -121,12 +122,25 @@ def conv3x3(P: Packed, name: str, x: Act, stride: int = 1, ups: int = 0, **epi) 
     return x.like(out, ho, wo)
 
 
+def _segment(fn):
+    """Marks a block as a SEGMENT of the differentiated forward: a clean function of its arguments (while a tape records, in-place skips, the LayerNorm /
+    upsampler folds, head-major K/V and the CFG prefix are off and single assignment holds), which a checkpointing recorder may keep by its boundary
+    tensors alone and run a second time in the backward walk (autodiff.Recorder.segment).  `ops.segment` is the one hook; a backend without it -- every
+    non-recording path -- gets the plain call, so no launch list changes."""
+    @functools.wraps(fn)
+    def run(P, p, *args, **kw):
+        hook = getattr(ops, "segment", None)
+        return fn(P, p, *args, **kw) if hook is None else hook(p, fn, (P, p, *args), kw)
+    return run
+
+
 def ups_fold_on() -> bool:
     """The folded form of the upsampler convolutions: when the backend has it (the CPU emulation does not), outside a differentiated run (gemm_dx
     differentiates ups = 1) and unless ME_UPS_FOLD=0 (A/B switch, read per call)."""
     return not getattr(ops, "recording", False) and getattr(ops, "UPS_FOLD", False) and __import__("os").environ.get("ME_UPS_FOLD", "1") != "0"
 
 
+@_segment
 def resnet_block(P: Packed, p: str, x: Act, temb: torch.Tensor, temb_off: int, *, per_frame_stats: bool, eps: float = 1e-5, shard=None,
                  out: Optional[torch.Tensor] = None) -> Act:
     """ResnetBlock2D.forward (resnet_2d.py:199-249).  GroupNorm statistics span all frames of a batch row
@@ -346,6 +360,7 @@ def basic_block(P: Packed, p: str, x: Act, text: Optional[torch.Tensor], text_se
     return x.like(t)
 
 
+@_segment
 def transformer2d(P: Packed, p: str, x: Act, text, text_seg, *, spatial=None, temporal=None, place: str = "", sc_attn: bool = True,
                   has_temp: bool = True, shard=None, out: Optional[torch.Tensor] = None, text_kv: Optional[dict] = None, expand: int = 1, branches=None) -> Act:
     """Transformer2DModel.forward (attention_2d.py:338-389): per-frame GroupNorm(32, eps 1e-6), 1x1 proj in/out.
@@ -412,6 +427,7 @@ def text_kv_all(P: Packed, text: torch.Tensor, names: List[str]) -> dict:
 # ---------------------------------------------------------------------------------------------
 # ControlAdapter (controlnet_adapter.py:437-565)
 # ---------------------------------------------------------------------------------------------
+@_segment
 def adapter_block(P: Packed, p: str, x: Act, src, nb: Optional[int] = None, shard=None) -> torch.Tensor:
     """ResnetBlock.forward (controlnet_adapter.py:497-534).  x: ControlNet residual rows [(b t N), C];
     src: UNet edit-branch skip rows [(nb t N), C], or a list of nb row tensors [(t N), C] (the edit rows of the batch-4 skip, read in

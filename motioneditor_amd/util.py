@@ -73,8 +73,24 @@ def _loss_scale(amax: float) -> float:
     return 2.0 ** math.floor(math.log2(64.0 / amax)) if amax > 0.0 and math.isfinite(amax) else 1.0
 
 
+def _checkpointing(unet, gradient_checkpointing: Optional[bool]) -> bool:
+    """An entry point's `gradient_checkpointing=`: None reads the model's flag (unet.enable_gradient_checkpointing())."""
+    return bool(getattr(unet, "gradient_checkpointing", False)) if gradient_checkpointing is None else bool(gradient_checkpointing)
+
+
+def _tape_stats(stats: Optional[dict], tape=None, G=None) -> None:
+    """What the tape held (autodiff.Tape.stashed_bytes, read at the end of the forward) and the gradient store's high-water mark, for callers that ask."""
+    if stats is None:
+        return
+    if tape is not None:
+        stats["stashed_bytes"] = tape.stashed_bytes()
+    if G is not None:
+        stats["grad_peak_bytes"], stats["grad_total_bytes"] = G.peak_bytes, G.total_bytes
+
+
 def null_optimization(pipeline, ddim_scheduler, latents, context: torch.Tensor, null_inner_steps: int = 10, epsilon: float = 1e-5,
-                      num_ddim_steps: Optional[int] = None, guidance_scale: float = 7.5, grads: Optional[list] = None) -> List[torch.Tensor]:
+                      num_ddim_steps: Optional[int] = None, guidance_scale: float = 7.5, grads: Optional[list] = None,
+                      gradient_checkpointing: Optional[bool] = None, stats: Optional[dict] = None) -> List[torch.Tensor]:
     """MyNullInversion.null_optimization: for each DDIM step a fresh Adam (lr 1e-2 (1 - i / 100)) moves the unconditional text
     embedding so that the guided prev_step of the current latent reproduces the inversion latent one step earlier; early stop at
     loss < epsilon + 2e-5 i; the latent then advances with the optimised embedding.  latents = the DDIM inversion trajectory
@@ -85,7 +101,12 @@ def null_optimization(pipeline, ddim_scheduler, latents, context: torch.Tensor, 
     comes from motioneditor_amd.autodiff (a tape over the C-ABI operators and their backward kernels) and the loss (me_mse_seed +
     me_sumsq_absmax), the loss-scale selection and Adam (me_adamw on the fp32 embedding) are device kernels too: the host reads two
     floats per inner step (the loss for the early stop, the seed's largest element for the loss scale).  As in the reference
-    (`:49-51` hard-codes it) the UNet runs with normal_infer=False -- sparse-causal attn1 -- and without editors."""
+    (`:49-51` hard-codes it) the UNet runs with normal_infer=False -- sparse-causal attn1 -- and without editors.
+
+    The tape is recorded towards the text rows (autodiff.record(wrt=)): what is not downstream of them is neither logged nor kept.
+    gradient_checkpointing (default: the flag unet.enable_gradient_checkpointing() sets): the UNet's blocks keep their boundary tensors only
+    and are recomputed in the backward walk -- same gradient bit for bit, one more forward of the differentiated blocks.
+    stats: a dict that receives the last inner step's stashed_bytes / grad_peak_bytes / grad_total_bytes."""
     from . import autodiff
     from .models import graph
     B_ = graph.ops
@@ -93,6 +114,7 @@ def null_optimization(pipeline, ddim_scheduler, latents, context: torch.Tensor, 
     P = unet.P
     dev = unet.device
     n = len(ddim_scheduler.timesteps) if num_ddim_steps is None else num_ddim_steps
+    ckpt = _checkpointing(unet, gradient_checkpointing)
     uncond0, cond = context.to(dev).float().chunk(2)
     cond_rows = graph.text_rows(cond, P.dtype)
     out: List[torch.Tensor] = []
@@ -113,8 +135,9 @@ def null_optimization(pipeline, ddim_scheduler, latents, context: torch.Tensor, 
         eps_c = graph.unet_forward(P, latent_cur, float(t), cond_rows).t          # rows [(f h w), 4]
         for k in range(null_inner_steps):
             text = text_of(uncond)
-            with autodiff.record(graph) as tape:
+            with (autodiff.record(graph) if autodiff.PARENT_FORM else autodiff.record(graph, wrt=[text], checkpoint=ckpt)) as tape:
                 act = graph.unet_forward(P, latent_cur, float(t), text)
+            _tape_stats(stats, tape=tape)
             # rec = prev_step(eps_u + g (eps_c - eps_u)) (:26-36), loss = mse(rec, latent_prev), d loss / d eps_u in the UNet's row layout
             diff, d_rows = B_.mse_seed(act.t, latent_prev, eps_c=eps_c, x=latent_cur, guidance=guidance_scale, ca=ca, cb=cb,
                                        coef=(2.0 / nel) * cb * (1.0 - guidance_scale))
@@ -123,6 +146,7 @@ def null_optimization(pipeline, ddim_scheduler, latents, context: torch.Tensor, 
             ls = _loss_scale(st[3])
             G = autodiff.backward(tape, [(act.t, d_rows)], seed_scale=ls, wrt=[text])   # only what lies downstream of the text rows is walked
             g = G.view(text)
+            _tape_stats(stats, G=G)
             if grads is not None:      # test hook (not part of the reference): the un-scaled gradient of this inner step
                 grads.append((g / ls).reshape(uncond0.shape).clone())
             B_.adamw(uncond, m_, v_, g.contiguous(), lr=lr, step=k + 1, grad_scale=1.0 / ls)
@@ -139,11 +163,13 @@ def null_optimization(pipeline, ddim_scheduler, latents, context: torch.Tensor, 
 # Adapter training step, the arithmetic of train_adaptor.py:364-368
 # ---------------------------------------------------------------------------------------------------------------------
 def _unet_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, trainable, param_buffers=None,
-                   sync_amax=None):
+                   sync_amax=None, gradient_checkpointing: Optional[bool] = None, stats: Optional[dict] = None):
     """Forward on the tape, loss, backward.  -> (loss, loss scale, gradient store); the gradients of the packed tensors `trainable()` names after the
     forward (autodiff.backward's `trainable`; packed layouts, times the loss scale) are accumulated into `param_buffers[key]` when given.  No residuals (None, None): the plain UNet forward.
     sync_amax: callable(tensor [2]) that makes the seed magnitude -- and with it the loss scale -- the same on every data-parallel rank (a MAX
-    all-reduce), so that the gradient buckets can be summed."""
+    all-reduce), so that the gradient buckets can be summed.
+    The tape is recorded towards the trained tensors (autodiff.record(trainable=)): `trainable` is asked again whenever the weight store has packed
+    something new, so that a call's weight is known as the call is recorded.  gradient_checkpointing / stats: as in null_optimization."""
     from . import autodiff
     from .models import graph
     B_ = graph.ops
@@ -154,8 +180,16 @@ def _unet_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_bl
     mid = None if mid_block_res_sample is None else rows(mid_block_res_sample)
     ehs = graph.text_rows(encoder_hidden_states.to(dev), P.dtype).clone()
     t = float(timestep.item() if torch.is_tensor(timestep) else timestep)
-    with autodiff.record(graph) as tape:
+    known = [-1, None]
+
+    def current():   # packed tensors come into being at their first use: re-read when the store has grown
+        if known[0] != len(P.cache):
+            known[0], known[1] = len(P.cache), trainable()
+        return known[1]
+    with (autodiff.record(graph) if autodiff.PARENT_FORM else
+          autodiff.record(graph, trainable=current, checkpoint=_checkpointing(unet, gradient_checkpointing))) as tape:
         act = graph.unet_forward(P, noisy_latents.to(dev), t, ehs, down_res=down, mid_res=mid, two_branch=False)
+    _tape_stats(stats, tape=tape)
     tgt = target.to(dev).float().contiguous()
     diff, d_rows = B_.mse_seed(act.t, tgt, coef=2.0 / tgt.numel())          # loss = mse(model_pred, target) (:368)
     amax = B_.sumsq_absmax(d_rows)
@@ -164,18 +198,21 @@ def _unet_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_bl
     st = torch.cat([B_.sumsq_absmax(diff), amax]).tolist()
     loss, ls = st[0] / tgt.numel(), _loss_scale(st[3])
     G = autodiff.backward(tape, [(act.t, d_rows)], trainable=trainable(), seed_scale=ls, param_buffers=param_buffers)
+    _tape_stats(stats, G=G)
     return loss, ls, G
 
 
 def adapter_training_grads(unet, noisy_latents: torch.Tensor, timestep, encoder_hidden_states: torch.Tensor, down_block_res_samples, mid_block_res_sample,
-                           target: torch.Tensor, prefix: str = "controlnet_adapter."):
+                           target: torch.Tensor, prefix: str = "controlnet_adapter.", gradient_checkpointing: Optional[bool] = None,
+                           stats: Optional[dict] = None):
     """loss = mse(unet(noisy, t, ehs, down_block_additional_residuals, mid_block_additional_residual), target) on ONE clip and its gradient
     w.r.t. every parameter under `prefix`, keyed by the reference's parameter names and in the reference's layouts (host tensors) -- what
     `accelerator.backward(loss)` leaves in `.grad` of the adapter (the reference trains nothing else: train_adaptor.py freezes the
     rest).  Residuals in the reference layout [b, C, f, h', w'] (ControlNet outputs, no gradient).  The forward is the ordinary
     launch graph on an autodiff tape.  This is the inspection / export form; the training step itself (AdapterTrainer) keeps the gradients
-    on the device in the packed layouts."""
-    loss, ls, G = _unet_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, lambda: unet.P.trainable_ids(prefix))
+    on the device in the packed layouts.  gradient_checkpointing / stats: as in null_optimization."""
+    loss, ls, G = _unet_backward(unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target, lambda: unet.P.trainable_ids(prefix),
+                                 gradient_checkpointing=gradient_checkpointing, stats=stats)
     grads = {}
     for key, g in G.params.items():
         for name, gn in unet.P.unpack_grad(key, g).items():    # host copy in the reference layout
@@ -192,12 +229,14 @@ class AdapterTrainer:
     (0.9, 0.999), weight decay 1e-2, eps 1e-8) on fp32 masters kept in the same packed layout, and the fp16 weights the forward reads
     refreshed IN PLACE from the masters by one cast kernel -- no gradient, master or optimiser state ever visits the host.  The loss is
     averaged over the ranks for logging as `:377` does.  `export_state_dict()` returns the trained parameters under the reference's names
-    and layouts (what train_adaptor.py saves as the adapter checkpoint)."""
+    and layouts (what train_adaptor.py saves as the adapter checkpoint).  gradient_checkpointing: None follows unet.enable_gradient_checkpointing();
+    `tape_stats`, when set to a dict, receives each step's stashed_bytes / grad_peak_bytes / grad_total_bytes."""
 
     def __init__(self, unet, lr: float = 3e-5, betas=(0.9, 0.999), weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0,
-                 prefix: str = "controlnet_adapter.", group=None):
+                 prefix: str = "controlnet_adapter.", group=None, gradient_checkpointing: Optional[bool] = None):
         from .models import graph
         self.unet, self.prefix, self.group, self.max_grad_norm = unet, prefix, group, max_grad_norm
+        self.gradient_checkpointing, self.tape_stats = gradient_checkpointing, None
         self.lr, self.betas, self.weight_decay, self.eps = lr, betas, weight_decay, eps
         self.steps = 0
         self.skipped_steps = 0           # optimisation steps dropped because the gradient norm was not finite (fp16 overflow)
@@ -241,7 +280,8 @@ class AdapterTrainer:
         if dist_on:
             sync = lambda a: dist.all_reduce(a, op=dist.ReduceOp.MAX, group=self.group)   # noqa: E731  (one loss scale for every rank's bucket)
         loss, ls, G = _unet_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, down_block_res_samples, mid_block_res_sample, target,
-                                     lambda: self.unet.P.trainable_ids(self.prefix), param_buffers=self.param_buffers, sync_amax=sync)
+                                     lambda: self.unet.P.trainable_ids(self.prefix), param_buffers=self.param_buffers, sync_amax=sync,
+                                     gradient_checkpointing=self.gradient_checkpointing, stats=self.tape_stats)
         stray = [k for k in G.params if k not in self.param_buffers]
         if stray:
             raise RuntimeError(f"a gradient reached packed tensors the trainer does not own: {stray[:3]}")
@@ -294,13 +334,14 @@ class UNetTuner:
     the inference forward, the folded upsampler weights (me_refresh_ups4) -- is rewritten IN PLACE after each update by one me_refresh_weights
     launch, so that recorded plans and captured graphs replay with the tuned weights; a derived tensor first built after tuning started is built from the live fp32 masters
     (weights.Packed.live).  No gradient, master or optimiser moment visits the host.  `save_checkpoint(dir)` writes what stage 2 and
-    inference read back (checkpoint.load_unet_state_dict(resume_from_checkpoint=dir))."""
+    inference read back (checkpoint.load_unet_state_dict(resume_from_checkpoint=dir)).  gradient_checkpointing / `tape_stats`: as AdapterTrainer."""
 
     def __init__(self, unet, trainable_modules=("attn1.to_q", "attn2.to_q", "attn_temp"), trainable_params=(), lr: float = 3e-5, betas=(0.9, 0.999),
-                 weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, group=None):
+                 weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, group=None, gradient_checkpointing: Optional[bool] = None):
         from .models import graph
         from .weights import select_trainable
         self.unet, self.group, self.max_grad_norm = unet, group, max_grad_norm
+        self.gradient_checkpointing, self.tape_stats = gradient_checkpointing, None
         self.lr, self.betas, self.weight_decay, self.eps = lr, betas, weight_decay, eps
         self.steps = 0
         self.skipped_steps = 0
@@ -453,7 +494,7 @@ class UNetTuner:
         self.grad.zero_()
         sync = (lambda a: dist.all_reduce(a, op=dist.ReduceOp.MAX, group=self.group)) if dist_on else None
         loss, ls, G = _unet_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, None, None, target, lambda: self.trainable,
-                                     param_buffers=self.param_buffers, sync_amax=sync)
+                                     param_buffers=self.param_buffers, sync_amax=sync, gradient_checkpointing=self.gradient_checkpointing, stats=self.tape_stats)
         stray = [k for k in G.params if k not in self.param_buffers]
         if stray:
             raise RuntimeError(f"a gradient reached packed tensors the tuner does not own: {stray[:3]}")
@@ -478,7 +519,7 @@ class UNetTuner:
         of every parameter in the bucket -- what loss.backward() leaves in .grad on the reference."""
         self.grad.zero_()
         loss, ls, G = _unet_backward(self.unet, noisy_latents, timestep, encoder_hidden_states, None, None, target, lambda: self.trainable,
-                                     param_buffers=self.param_buffers)
+                                     param_buffers=self.param_buffers, gradient_checkpointing=self.gradient_checkpointing)
         del G
         out = {n: self._reference_layout(n, self.param_buffers[n] / ls).cpu().contiguous() for n in self.names}
         self.grad.zero_()

@@ -267,6 +267,8 @@ extern "C" void me_set_error(const char* msg);
 
 extern "C" void me_set_hip_error(const char* what, int err);
 
+extern "C" void me_set_kernel(const char* name);
+
 #define ME_CHECK_LAUNCH(name)                                         \
   {                                                                   \
     const hipError_t e_ = hipGetLastError();                          \
@@ -286,6 +288,7 @@ extern "C" int me_conv_small(const me_conv_small_args* a, void* stream) {
     (void)hipGetLastError();
     if (a->Cin == 3) hipLaunchKernelGGL(conv_small_tile_kernel<3>, dim3((unsigned)((npix + 63) / 64)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), *a);
     else hipLaunchKernelGGL(conv_small_tile_kernel<4>, dim3((unsigned)((npix + 63) / 64)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), *a);
+    me_set_kernel(a->Cin == 3 ? "conv_small_tile_kernel<3>" : "conv_small_tile_kernel<4>");
     ME_CHECK_LAUNCH("me_conv_small")
   }
   const int co_per_block = a->Cout > 80 ? 80 : a->Cout;   // wide outputs: slices of 80 channels per block row
@@ -293,6 +296,7 @@ extern "C" int me_conv_small(const me_conv_small_args* a, void* stream) {
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   if (a->Cin == 3) hipLaunchKernelGGL(conv_small_kernel<3>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a, co_per_block);
   else hipLaunchKernelGGL(conv_small_kernel<4>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *a, co_per_block);
+  me_set_kernel(a->Cin == 3 ? "conv_small_kernel<3>" : "conv_small_kernel<4>");
   ME_CHECK_LAUNCH("me_conv_small")
 }
 
@@ -302,6 +306,7 @@ extern "C" int me_axpy_rows(void* Y, int32_t ldy, const void* X, int32_t ldx, co
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(axpy_rows_kernel, dim3(grid_for(rows * (cols / 4))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(Y), ldy,
                      reinterpret_cast<const f16*>(X), ldx, reinterpret_cast<const f16*>(A), lda, (long)rows, cols, alpha);
+  me_set_kernel("axpy_rows_kernel");
   ME_CHECK_LAUNCH("me_axpy_rows")
 }
 
@@ -310,6 +315,7 @@ extern "C" int me_copy_rows(void* Y, int32_t ldy, const void* X, int32_t ldx, in
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for(rows * (cols / 8))), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(Y), ldy,
                      reinterpret_cast<const f16*>(X), ldx, (long)rows, cols);
+  me_set_kernel("copy_rows_kernel");
   ME_CHECK_LAUNCH("me_copy_rows")
 }
 
@@ -321,6 +327,7 @@ extern "C" int me_copy_blocks(void* Y, int32_t ldy, const void* X, int32_t ldx, 
   const long total = (long)n0 * n1 * rows * (cols / 8);
   hipLaunchKernelGGL(copy_blocks_kernel, dim3(grid_for(total)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(Y), ldy,
                      reinterpret_cast<const f16*>(X), ldx, n1, (long)rows, cols, total, (long)ys0, (long)ys1, (long)xs0, (long)xs1);
+  me_set_kernel("copy_blocks_kernel");
   ME_CHECK_LAUNCH("me_copy_blocks")
 }
 
@@ -329,6 +336,7 @@ extern "C" int me_silu(void* Y, const void* X, int64_t n, void* stream) {
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(unary_kernel<0>, dim3(grid_for((n + 7) / 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(Y),
                      reinterpret_cast<const f16*>(X), (long)n);
+  me_set_kernel("unary_kernel<silu>");
   ME_CHECK_LAUNCH("me_silu")
 }
 
@@ -337,6 +345,7 @@ extern "C" int me_relu(void* Y, const void* X, int64_t n, void* stream) {
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(unary_kernel<1>, dim3(grid_for((n + 7) / 8)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(Y),
                      reinterpret_cast<const f16*>(X), (long)n);
+  me_set_kernel("unary_kernel<relu>");
   ME_CHECK_LAUNCH("me_relu")
 }
 
@@ -345,6 +354,7 @@ extern "C" int me_timestep_embed(void* out, int32_t rows, int32_t dim, float t, 
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(timestep_embed_kernel, dim3((rows * dim + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(out), rows,
                      dim, t, (const float*)nullptr);
+  me_set_kernel("timestep_embed_kernel");
   ME_CHECK_LAUNCH("me_timestep_embed")
 }
 
@@ -353,6 +363,7 @@ extern "C" int me_timestep_embed_dev(void* out, int32_t rows, int32_t dim, const
   (void)hipGetLastError();
   hipLaunchKernelGGL(timestep_embed_kernel, dim3((rows * dim + 255) / 256), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(out), rows,
                      dim, 0.f, step_params);
+  me_set_kernel("timestep_embed_kernel<dev>");
   ME_CHECK_LAUNCH("me_timestep_embed_dev")
 }
 
@@ -363,6 +374,7 @@ extern "C" int me_cfg_ddim(float* lat_out, const float* lat_in, const void* eps,
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(cfg_ddim_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), lat_out, lat_in,
                      reinterpret_cast<const f16*>(eps), lde, nb, C, frames, npix, guidance, ca, cb, (const float*)nullptr);
+  me_set_kernel("cfg_ddim_kernel");
   ME_CHECK_LAUNCH("me_cfg_ddim")
 }
 
@@ -373,6 +385,7 @@ extern "C" int me_cfg_ddim_dev(float* lat_out, const float* lat_in, const void* 
   (void)hipGetLastError();
   hipLaunchKernelGGL(cfg_ddim_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), lat_out, lat_in,
                      reinterpret_cast<const f16*>(eps), lde, nb, C, frames, npix, 0.f, 0.f, 0.f, step_params);
+  me_set_kernel("cfg_ddim_kernel<dev>");
   ME_CHECK_LAUNCH("me_cfg_ddim_dev")
 }
 
@@ -382,6 +395,7 @@ extern "C" int me_gaussian_sample(float* out, const void* moments, int32_t ldm, 
   (void)hipGetLastError();
   hipLaunchKernelGGL(gaussian_sample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), out,
                      reinterpret_cast<const f16*>(moments), ldm, noise, n_img, npix, scale);
+  me_set_kernel("gaussian_sample_kernel");
   ME_CHECK_LAUNCH("me_gaussian_sample")
 }
 
@@ -392,6 +406,7 @@ extern "C" int me_nchw_to_rows(void* Y, int32_t ldy, const float* X, int64_t img
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(nchw_to_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<f16*>(Y), ldy, X,
                      (long)img_stride, (long)ch_stride, n_img, C, npix);
+  me_set_kernel("nchw_to_rows_kernel");
   ME_CHECK_LAUNCH("me_nchw_to_rows")
 }
 
@@ -402,5 +417,6 @@ extern "C" int me_rows_to_nchw(float* Y, int64_t img_stride, int64_t ch_stride, 
   (void)hipGetLastError();  // drop stale errors left by other HIP users in this thread
   hipLaunchKernelGGL(rows_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), Y, (long)img_stride,
                      (long)ch_stride, reinterpret_cast<const f16*>(X), ldx, n_img, C, npix);
+  me_set_kernel("rows_to_nchw_kernel");
   ME_CHECK_LAUNCH("me_rows_to_nchw")
 }

@@ -22,6 +22,11 @@ its n_sample_frames and width / height) and saves the edit and the reconstructio
     python examples/run_edit.py --prompt "a girl is dancing" --target-prompt "a boy is dancing" --target-prompt "a robot is dancing" --out outputs/case-1
 edits the clip towards every --target-prompt (up to 3) in ONE call -- the reference loops over its prompts, one whole run each (inference.py:298-323); here
 the reconstruction branch is computed once per step and shared -- and saves sample/{target}.gif per target plus one -inv.gif.
+    python examples/run_edit.py --prompt "a girl is dancing" --target-prompt "a boy is dancing" --attention-maps girl --out outputs/case-1
+additionally collects the head-mean text cross-attention of the 16 x 16-token layers over the denoising steps (MutualAttentionBase.collect_cross_attention;
+the reference's cross_attns / aggregate_cross_attn_map, fully_control.py:257-277) and saves where the word's tokens look: sample/attn-girl-inv.gif (the
+reconstruction's conditional rows, tokens of the word in the source prompt) and sample/attn-girl.gif (the edits' conditional rows, tokens of the word in each
+target prompt).  --attention-map-tokens 1,2 names token positions instead of a word and works with the synthetic embeddings as well.
 """
 from __future__ import annotations
 
@@ -100,7 +105,43 @@ def extra_target_embeddings(n: int, seed: int = 33) -> torch.Tensor:
     return torch.from_numpy(synth.synth_normal("harness.cond.more", (n - 1, 77, 768), seed, 0.3))
 
 
-def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, output_type: str = "tensor", graphed: bool = False, prompts=None, n_targets: int = 1):
+def attention_tokens(a, prompts, tokenizer) -> dict:
+    """name -> [token positions per prompt]: --attention-maps WORD looks the word up in every prompt (tokenizer.word_indices = the reference's
+    get_word_inds, inference.py:304-311), --attention-map-tokens gives the positions themselves, the same for every prompt."""
+    out = {}
+    for word in a.attention_maps or []:
+        if prompts is None:
+            raise SystemExit("--attention-maps WORD looks the word up in the prompts: give --prompt (or name the token positions with --attention-map-tokens)")
+        out[word] = [tokenizer.word_indices(p, word) for p in prompts]
+        if not any(out[word]):
+            raise SystemExit(f"--attention-maps {word}: no prompt holds that word")
+    for spec in a.attention_map_tokens or []:
+        idx = [int(t) for t in spec.split(",")]
+        if not idx or min(idx) < 0 or max(idx) > 76:
+            raise SystemExit(f"--attention-map-tokens {spec}: token positions are 0 .. 76")
+        out["tokens-" + "-".join(map(str, idx))] = idx if prompts is None else [idx] * len(prompts)
+    return out
+
+
+def cross_attention_maps(sed, tokens, n_targets: int, f: int):
+    """(reconstruction maps [1, f, res, res], edit maps [N, f, res, res]) of the conditional rows of the batch [u.rec, u.e_1 .. u.e_N, c.rec, c.e_1 .. c.e_N].
+    tokens: one list of positions, or one list per prompt [source, target_1 .. target_N]; a prompt without the word gets a black map."""
+    per_prompt = tokens if tokens and isinstance(tokens[0], (list, tuple)) else [list(tokens)] * (1 + n_targets)
+    nb = 1 + n_targets
+    rows = []
+    for k, idx in enumerate(per_prompt):
+        b = nb + k                                                        # the conditional row of prompt k
+        if idx:
+            rows.append(sed.aggregate_cross_attn_map(list(idx))[b * f:(b + 1) * f])
+        else:
+            res = int(round(sed._xa_tokens ** 0.5))
+            rows.append(torch.zeros((f, res, res), device=sed._xa_acc.device))
+    maps = torch.stack(rows)
+    return maps[:1], maps[1:]
+
+
+def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, output_type: str = "tensor", graphed: bool = False, prompts=None, n_targets: int = 1,
+        attention_tokens=None, maps_out=None):
     """inference.py:259-326 for one (source prompt, target prompt) pair.  Returns (sample_inv, sample_gen, ddim_inv_latent).
     prompts = [source, target]: the pipeline's own text encoder and tokenizer encode them (and the empty prompt) instead of the tensors in `x`.
     prompts = [source, target_1 .. target_N] (or n_targets = N with the synthetic embeddings): every target in the one call, all towards the clip's one target
@@ -125,6 +166,8 @@ def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, out
     regiter_temporal_attention_editor_diffusers(pipe, ted)
     sed = FullySelfAttentionControlMask(start_step=4, start_layer=10, source_masks=x["source_masks"], target_masks=None, rectangle_source_masks=None)
     regiter_fully_attention_editor_diffusers(pipe, sed)
+    if attention_tokens:
+        sed.collect_cross_attention()        # the 16 x 16-token layers, every step, into one accumulator (the inversion above runs without editors: nothing collected)
     emb = {} if prompts else dict(text_embeddings=x["text_embeddings"], negative_text_embeddings=x["negative_text_embeddings"])
     if not prompts and n_targets > 1:
         emb["text_embeddings"] = torch.cat([x["text_embeddings"], extra_target_embeddings(n_targets).to(x["text_embeddings"].device)])
@@ -132,6 +175,10 @@ def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, out
                   guidance_scale=guidance, latents=ddim_inv_latent, uncond_embeddings=None, skeleton=skeleton, source_masks=None, target_masks=None,
                   rectangle_source_masks=None, background_latents=None, output_type=output_type, **emb).images
     assert sample.shape[0] == 1 + n_targets
+    if attention_tokens:
+        sed.stop_collecting()
+        for name, tokens in attention_tokens.items():
+            maps_out[name] = cross_attention_maps(sed, tokens, n_targets, f)
     sample_inv, sample_gen = sample[:1], sample[1:]
     return sample_inv, sample_gen, ddim_inv_latent
 
@@ -167,6 +214,11 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--target-prompt", action="append", default=None,
                     help="target prompt (default: the source prompt); give it several times (up to 3) to edit the clip towards every one of them in one call")
     ap.add_argument("--checkpoint", default=None, help="SD-1.5 directory whose text_encoder/ and tokenizer/ serve --prompt (default: synthetic weights and vocabulary)")
+    ap.add_argument("--attention-maps", action="append", default=None, metavar="WORD",
+                    help="with --prompt and --out: save where the tokens of WORD look (head-mean text cross-attention of the 16 x 16 layers, averaged over the steps) as "
+                         "sample/attn-WORD-inv.gif (reconstruction) and sample/attn-WORD.gif (edits); repeatable")
+    ap.add_argument("--attention-map-tokens", action="append", default=None, metavar="I,J",
+                    help="the same for the token positions I,J (1 = the first token after the start token); works with the synthetic embeddings; repeatable")
     add_clip_arguments(ap)
     ap.add_argument("--out", default=None, help="directory that receives sample/{target prompt}.gif (the edit) and sample/{target prompt}-inv.gif (the reconstruction)")
     return ap
@@ -183,7 +235,11 @@ def main():
     x = clip_inputs(a) if a.video_dir else {k: v.cuda() for k, v in harness_inputs(a.frames, a.size, a.size).items()}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps, prompts=prompts, n_targets=len(a.target_prompt or [None]))
+    want_maps = attention_tokens(a, prompts, pipe.tokenizer)
+    if want_maps and not a.out:
+        raise SystemExit("--attention-maps / --attention-map-tokens write GIFs: give --out")
+    maps = {}
+    inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps, prompts=prompts, n_targets=len(a.target_prompt or [None]), attention_tokens=want_maps, maps_out=maps)
     torch.cuda.synchronize()
     print(f"{a.frames} frames {a.size}x{a.size}: encode + {a.inv_steps} inversion steps + {a.steps} denoising steps + decode in {time.perf_counter() - t0:.2f} s; "
           f"reconstruction {tuple(inv.shape)}, edit {tuple(gen.shape)}, range [{float(gen.min()):.3f}, {float(gen.max()):.3f}]")
@@ -192,6 +248,10 @@ def main():
         if len(set(names)) != len(names):     # the same target twice: keep the files apart
             names = [f"{t} ({k + 1})" for k, t in enumerate(names)]
         print("saved", *save_samples(a.out, names, inv, gen))
+        from motioneditor_amd import util
+        for name, (m_inv, m_gen) in maps.items():
+            print("saved", util.save_attention_maps(m_inv, f"{a.out}/sample/attn-{name}-inv.gif", size=a.size),
+                  util.save_attention_maps(m_gen, f"{a.out}/sample/attn-{name}.gif", size=a.size))
 
 
 if __name__ == "__main__":

@@ -42,7 +42,7 @@ class FullySelfAttentionControlMask(MutualSelfAttentionControl):
         self.ref_token_idx = ref_token_idx
         self.cur_token_idx = cur_token_idx
         self.self_attns = []
-        self.cross_attns = []   # the reference appends head-mean 16x16 cross maps here and never reads them (:430-432)
+        self.cross_attns = []   # the reference appends head-mean 16x16 cross maps here (:430-432); filled by collect_cross_attention(keep_entries=True)
         self.cross_attns_mask = None
         self.self_attns_mask = None
         self.mask_save_dir = mask_save_dir

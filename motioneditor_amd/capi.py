@@ -57,6 +57,19 @@ class AttnArgs(C.Structure):
     ]
 
 
+class AttnProbsArgs(C.Structure):
+    """me_attn_probs_args (include/motioned_probe.h)."""
+    _fields_ = [
+        ("Q", _vp), ("K", _vp), ("P", _vp),
+        ("ldq", _i32), ("ldk", _i32), ("ldp", _i32),
+        ("heads", _i32), ("dh", _i32),
+        ("n_items", _i32), ("nq", _i32), ("nk", _i32),
+        ("kv_item", _vp), ("q_items", _i32),
+        ("hsq", _i64), ("hsk", _i64),
+        ("scale", _f32), ("alpha", _f32), ("beta", _f32),
+    ]
+
+
 class AttnBwdArgs(C.Structure):
     _fields_ = [
         ("Q", _vp), ("K", _vp), ("V", _vp), ("O", _vp), ("dO", _vp), ("lse", _vp), ("dQ", _vp), ("dK", _vp), ("dV", _vp), ("delta", _vp),
@@ -224,6 +237,12 @@ LONG_SYMBOLS = {
     "me_tattn_bwd_long_work_bytes": (_i64, [_i32, _i32, _i32, _i32]),
 }
 
+# every symbol include/motioned_probe.h declares (csrc/attn_probs.hip: the head-mean probabilities of the text cross-attention; a step that collects no
+# maps never calls it, so it stands outside the denoising-step ABI as well)
+PROBE_SYMBOLS = {
+    "me_attn_probs": (C.c_int, [C.POINTER(AttnProbsArgs), _vp]),
+}
+
 _lib = None
 
 
@@ -244,7 +263,7 @@ def lib() -> C.CDLL:
         # and every launch would then fail with hipErrorNoDevice -- so make sure torch is loaded first.
         import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS, **TUNE_SYMBOLS, **LONG_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS, **TUNE_SYMBOLS, **LONG_SYMBOLS, **PROBE_SYMBOLS}.items():
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         if L.me_abi_version() != ABI_VERSION:

@@ -76,6 +76,14 @@ class AttnCall:
         return ops.attention(self.q, self.k, self.v, heads=HEADS, dh=self.dh, n_items=self.B * self.f, nq=self.N, nk=self.nk,
                              seg_item=seg_item, seg_mode=seg_mode, mask=mask, **({"q_items": self.q_items} if self.q_items else {}))
 
+    def probs(self, seg_item: torch.Tensor, out: torch.Tensor, beta: float = 0.0) -> torch.Tensor:
+        """out [B f N, >= nk] fp32 = beta * out + the head-mean softmax probabilities of this call over the keys of its ONE segment (the text cross
+        table: seg_item [B f, 1] is the kv item of every query item) -- what the reference's editors keep of a cross-attention (fully_control.py:430-432)."""
+        if seg_item.dim() != 2 or seg_item.shape[1] != 1:
+            raise ValueError("AttnCall.probs: a one-segment table (the text cross-attention) is expected")
+        return ops.attention_probs(self.q, self.k, heads=HEADS, dh=self.dh, n_items=self.B * self.f, nq=self.N, nk=self.nk, kv_item=seg_item.reshape(-1),
+                                   out=out, beta=beta, **({"q_items": self.q_items} if self.q_items else {}))
+
 
 @dataclass
 class TemporalCall:

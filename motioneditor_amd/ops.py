@@ -1092,3 +1092,7 @@ def refresh_weights(table: RefreshTable) -> None:
         capi.check(capi.lib().me_refresh_weights(table.buf.data_ptr(), table.n, table.total_rows, _stream()), "me_refresh_weights")
     for m, d in table.ups4:
         capi.check(capi.lib().me_refresh_ups4(d.data_ptr(), m.data_ptr(), m.shape[0], m.shape[2], _stream()), "me_refresh_ups4")
+
+
+# The cross-attention probe (include/motioned_probe.h): ops.attention_probs, written in probe.py
+from .probe import attention_probs  # noqa: E402,F401

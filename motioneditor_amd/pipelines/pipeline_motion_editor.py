@@ -38,6 +38,18 @@ class MotionEditorPipelineOutput:
 MAX_TARGETS = segments.TATTN_MAX_BATCH // 2 - 1   # 2 (1 + N) batch rows per step; one temporal-attention launch holds 8 (me_tattn_args.kv_map)
 
 
+def _collecting(editor) -> bool:
+    """Does the spatial editor collect cross-attention maps in the coming step (MutualAttentionBase.collect_cross_attention)?"""
+    fn = getattr(editor, "collects_in_step", None)
+    return bool(fn()) if fn is not None else False
+
+
+def _no_collection(editor, what: str) -> None:
+    if _collecting(editor):
+        raise NotImplementedError(f"{what} does not support cross-attention collection (collect_cross_attention): the accumulator is one device buffer of the "
+                                  "full batch and the host counts its entries per executed layer -- use denoise_step or denoise_step_planned, or stop_collecting()")
+
+
 def _single_target_only(latents: torch.Tensor, what: str) -> None:
     if latents.shape[0] > 2:
         raise NotImplementedError(f"{what} runs one (recon, edit) pair: N > 1 targets (latents batch {latents.shape[0]} = 1 + N) are supported by "
@@ -260,6 +272,7 @@ class MotionEditorPipeline:
         rank 1: the conditional ones), which halves every frame-shard exchange (batch 2 instead of 4); the pair trades its
         4-channel noise predictions with one all-gather before the fused CFG + DDIM update."""
         _single_target_only(latents, "denoise_step_frame_sharded")
+        _no_collection(self.unet.spatial_editor, "denoise_step_frame_sharded")
         if shard.f_total % 2:
             raise NotImplementedError("frame sharding relies on the ControlNet batch-entry identity, which needs an even frame count")
         f = latents.shape[2]
@@ -322,6 +335,7 @@ class MotionEditorPipeline:
         exchange is ONE all-gather of the 4-channel noise prediction (RCCL over xGMI on MI355X; 2 x [2,4,f,h,w] fp16) before
         the fused CFG + DDIM update, which every rank then applies to its own copy of the latents."""
         _single_target_only(latents, "denoise_step_cfg_parallel")
+        _no_collection(self.unet.spatial_editor, "denoise_step_cfg_parallel")
         from .. import parallel
         cx = parallel.exchange(group)                      # a torch process group, or an exchange adapter (direct RCCL for graph capture)
         r = cx.rank
@@ -421,7 +435,11 @@ class MotionEditorPipeline:
         """What the editors will do during the coming step: a pure function of their step counters (fully_control.py:434,
         temporal_control.py:74), so two captured graphs (editors inactive / active) cover a whole run."""
         sed, ted = self.unet.spatial_editor, self.unet.temporal_editor
-        return (None if sed is None else sed.cur_step in sed.step_idx, None if ted is None else ted.cur_step in ted.step_idx)
+        gate = (None if sed is None else sed.cur_step in sed.step_idx, None if ted is None else ted.cur_step in ted.step_idx)
+        # a step that collects cross-attention maps holds one more launch per collected layer (and the accumulator's address): a key of its own, so that a
+        # plan recorded without the probe is never replayed with it, or the reverse.  Not collecting: the key is what it was
+        # (the editor's identity too: the recorded probes hold the address of ITS accumulator; the plan keeps the editor alive, so the id stays its own)
+        return gate + (("xattn", sed._xa_tokens, id(sed)),) if _collecting(sed) else gate
 
     @torch.no_grad()
     def denoise_step_graphed(self, latents: torch.Tensor, t: int, text_embeddings_input: torch.Tensor, images: Optional[torch.Tensor],
@@ -437,6 +455,7 @@ class MotionEditorPipeline:
         process group enqueues on its streams, which fork from and join the capturing stream); every rank of the groups involved must
         capture and replay in step."""
         _single_target_only(latents, "denoise_step_graphed")
+        _no_collection(self.unet.spatial_editor, "denoise_step_graphed")
         from .. import parallel
         sed, ted = self.unet.spatial_editor, self.unet.temporal_editor
         if shard is not None:
@@ -531,9 +550,18 @@ class MotionEditorPipeline:
             editors = [e for e in (sed, ted) if e is not None]
             counters = [(e.cur_step, e.cur_att_layer) for e in editors]
 
+            # the first step is computed three times (warm-up, recording, replay): a collecting editor would sum its maps three times over
+            collecting = _collecting(sed)
+            if collecting and getattr(sed, "_xa_keep", False):
+                raise ValueError("denoise_step_planned: collect_cross_attention(keep_entries=True) is for the eager executor (denoise_step) only -- a replayed step "
+                                 "runs no Python per layer, so nothing would append to cross_attns")
+            maps = sed.cross_attention_state() if collecting else None
+
             def rewind():
                 for e, (cs, cl) in zip(editors, counters):
                     e.cur_step, e.cur_att_layer = cs, cl
+                if collecting:
+                    sed.restore_cross_attention(maps)
 
             st = dict(lat=latents.clone(), emb=emb.clone(), params=torch.tensor([float(t), float(guidance_scale), ca, cb], dtype=torch.float32).to(latents.device))
             step = lambda: self.denoise_step(st["lat"], t, st["emb"], images, guidance_scale, controlnet_conditioning_scale)   # noqa: E731
@@ -547,6 +575,7 @@ class MotionEditorPipeline:
                 with pl.recording():
                     st["out"] = step()
                 torch.cuda.synchronize()
+                st["xattn_entries"] = sed._xa_count - maps[1] if collecting else 0      # probe launches of one step: what a replay adds to the host's count
                 pl.bind(st["lat"], st["emb"], st["params"], st["out"])
             except BaseException:
                 # the warm-up or the recording pass raised part-way through a step: the editors' (cur_step, cur_att_layer) counters have advanced by a
@@ -560,11 +589,15 @@ class MotionEditorPipeline:
                 ops.STEP_PARAMS = None
             rewind()
             st["plan"] = pl
+            if collecting:
+                st["xattn_editor"] = sed       # the accumulator the recorded probes add into
             st["images"] = images          # keep the conditioning tensor the recorded launches read alive ...
             if self.controlnet is not None:   # ... and the conditioning embedding computed from it (graph.controlnet_forward's table may drop it later)
                 st["cond_embed"] = dict(self.controlnet.P.cache.get("cond_embed", {}))
             ent = self._cache_put(self._plans, key, st)
         out = ent["plan"].step(latents, emb, float(t), float(guidance_scale), ca, cb)
+        if ent.get("xattn_entries"):
+            sed._xa_count += ent["xattn_entries"]
         for e in (sed, ted):
             if e is not None:      # what MutualAttentionBase.__call__ does over the step's attention layers
                 e.cur_att_layer = 0

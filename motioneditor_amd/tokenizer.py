@@ -198,6 +198,29 @@ class CLIPTokenizer:
             raw.extend(bytes([b]) if b is not None else ch.encode("utf-8"))
         return raw.decode("utf-8", errors="replace").replace(EOW, " ").strip()
 
+    # -- word -> token positions
+    def word_indices(self, text: str, word) -> List[int]:
+        """Positions (1-based: 0 is the start token) of the tokens of `word` in the encoding of `text`: get_word_inds of the reference
+        (inference.py:52-71, p2p/seq_aligner.py:118-136).  `word` is a word of `text.split(" ")` (every occurrence counts), or an int: the place of the
+        word in that split.  A word the prompt does not hold gives []; a word of several tokens gives every one of them.  Tokens are assigned
+        to the split words by length: a word is complete once the decoded tokens since the last word boundary cover its characters."""
+        words = text.split(" ")
+        wanted = {i for i, w in enumerate(words) if w == word} if isinstance(word, str) else ({int(word)} if isinstance(word, int) else {int(i) for i in word})
+        if not wanted:
+            return []
+        pieces = [self.decode([i]).strip("#") for i in self.encode(text)[1:-1]]
+        hits: List[int] = []
+        at, seen = 0, 0                      # the split word being spelt, and how many of its characters the tokens so far have covered
+        for pos, piece in enumerate(pieces, start=1):
+            if at >= len(words):
+                break
+            if at in wanted:
+                hits.append(pos)
+            seen += len(piece)
+            if seen >= len(words[at]):
+                at, seen = at + 1, 0
+        return hits
+
     # -- the call of the pipeline
     def __call__(self, text: Union[str, Sequence[str]], padding="max_length", max_length: int = None, truncation: bool = True, return_tensors: str = "pt"):
         if padding != "max_length" or return_tensors != "pt":

@@ -594,3 +594,29 @@ def save_videos_as_images(videos: torch.Tensor, path: str, rescale=False, n_rows
         os.makedirs(save_dir, exist_ok=True)
         for frame_idx, image in enumerate(frames):
             Image.fromarray(image).save(os.path.join(save_dir, f"frame_{frame_idx}.png"))
+
+
+def save_attention_maps(maps: torch.Tensor, path: str, size: int = 256, fps: int = GIF_FPS):
+    """Cross-attention heat maps as a GIF: maps [b, f, h, w] in [0, 1] (MutualAttentionBase.aggregate_cross_attn_map reshaped to its batch rows; NaN -- a
+    constant map -- shows as black) -> grey frames, every map pixel a (size / h) x (size / w) block (nearest upsampling), the b maps of a frame side by
+    side through the grid writer of the videos (ops.video_grid_u8), `fps` frames per second."""
+    import os
+    from PIL import Image
+    if not torch.is_tensor(maps) or maps.dim() != 4:
+        raise ValueError("save_attention_maps: expected a tensor [b, f, h, w]")
+    if str(path).lower().endswith(".mp4"):
+        raise ValueError(f"save_attention_maps: {path}: give a .gif path")
+    b, f, h, w = maps.shape
+    size, fps = int(size), int(fps)
+    if size < max(h, w) or fps <= 0:
+        raise ValueError(f"save_attention_maps: size must be at least the map's {max(h, w)} pixels and fps positive, got size {size}, fps {fps}")
+    m = maps.detach().float().nan_to_num(0.0).clamp(0.0, 1.0)
+    iy = (torch.arange(size, device=m.device) * h) // size          # nearest: output pixel y shows map row floor(y h / size)
+    ix = (torch.arange(size, device=m.device) * w) // size
+    video = m[:, :, iy][:, :, :, ix][:, None].contiguous()          # [b, 1, f, size, size]
+    frames = videos_to_grid_frames(video).numpy()
+    if os.path.dirname(path):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+    ims = [Image.fromarray(fr) for fr in frames]
+    ims[0].save(path, format="GIF", save_all=True, append_images=ims[1:], loop=0, duration=max(1000 // fps, 1))
+    return path

@@ -183,6 +183,36 @@ def run(pipe, x: dict, *, steps: int, inv_steps: int, guidance: float = 7.5, out
     return sample_inv, sample_gen, ddim_inv_latent
 
 
+# `--metrics synthetic`: the token geometry of ViT-L/14 (257 tokens) at a reduced width, seeded weights
+SYNTHETIC_CLIP_VISION = dict(hidden_size=256, num_hidden_layers=3, num_attention_heads=4, intermediate_size=1024, image_size=224, patch_size=14, projection_dim=64)
+SYNTHETIC_CLIP_TEXT = dict(hidden_size=256, num_hidden_layers=2, num_attention_heads=4, intermediate_size=512, projection_dim=64)
+
+
+def metric_models(spec: str, device: str = "cuda"):
+    """(CLIPModel, CLIPImageProcessor, CLIPTokenizer) of --metrics: one CLIP checkpoint directory, or "synthetic"."""
+    from motioneditor_amd.models.clip import CLIPImageProcessor, CLIPModel
+    from motioneditor_amd.tokenizer import CLIPTokenizer
+    if spec == "synthetic":
+        tok = CLIPTokenizer.from_synthetic()
+        text = dict(SYNTHETIC_CLIP_TEXT, vocab_size=len(tok), eos_token_id=tok.eos_token_id)
+        return CLIPModel.from_synthetic(device, text_config=text, vision_config=SYNTHETIC_CLIP_VISION), CLIPImageProcessor(device=device), tok
+    return CLIPModel.from_pretrained(spec, device=device), CLIPImageProcessor.from_pretrained(spec, device=device), CLIPTokenizer.from_pretrained(spec, subfolder=None)
+
+
+def score(spec: str, x: dict, sample_inv, sample_gen, prompts=None, names=None, device: str = "cuda") -> dict:
+    """The CLIP metrics of one run: {"source": {...}, "reconstruction": {...}, "edits": {name: {...}}}.  Frame consistency of all three; text alignment (with
+    `prompts` = [source, target_1 .. target_N]) of the reconstruction against the source prompt and of every edit against its own target."""
+    from motioneditor_amd import metrics
+    model, processor, tok = metric_models(spec, device)
+    source = ((x["pixel_values"].float() + 1.0) / 2.0).permute(0, 2, 1, 3, 4).contiguous()       # [1, f, 3, H, W] in [-1, 1] -> [1, 3, f, H, W] in [0, 1]
+    names = list(names) if names else [f"edit {k + 1}" for k in range(sample_gen.shape[0])]
+    out = {"clip": spec, "source": metrics.clip_metrics(source, None, model, processor),
+           "reconstruction": metrics.clip_metrics(sample_inv, prompts[0] if prompts else None, model, processor, tok), "edits": {}}
+    for k, name in enumerate(names):
+        out["edits"][name] = metrics.clip_metrics(sample_gen[k:k + 1], prompts[1 + k] if prompts else None, model, processor, tok)
+    return out
+
+
 def text_models(checkpoint=None, device: str = "cuda"):
     """(text_encoder, tokenizer): the native CLIP classes from an SD-1.5 checkpoint directory, or synthetic ones."""
     from motioneditor_amd.models.clip import CLIPTextModel
@@ -219,6 +249,9 @@ def parser() -> argparse.ArgumentParser:
                          "sample/attn-WORD-inv.gif (reconstruction) and sample/attn-WORD.gif (edits); repeatable")
     ap.add_argument("--attention-map-tokens", action="append", default=None, metavar="I,J",
                     help="the same for the token positions I,J (1 = the first token after the start token); works with the synthetic embeddings; repeatable")
+    ap.add_argument("--metrics", default=None, metavar="CLIP_DIR|synthetic",
+                    help="with --out: score source, reconstruction and edits with the CLIP metrics (frame consistency; text alignment with --prompt) on the native CLIP "
+                         "image encoder and write sample/metrics.json; CLIP_DIR = one CLIP checkpoint directory, 'synthetic' = small seeded towers")
     add_clip_arguments(ap)
     ap.add_argument("--out", default=None, help="directory that receives sample/{target prompt}.gif (the edit) and sample/{target prompt}-inv.gif (the reconstruction)")
     return ap
@@ -238,6 +271,8 @@ def main():
     want_maps = attention_tokens(a, prompts, pipe.tokenizer)
     if want_maps and not a.out:
         raise SystemExit("--attention-maps / --attention-map-tokens write GIFs: give --out")
+    if a.metrics and not a.out:
+        raise SystemExit("--metrics writes sample/metrics.json: give --out")
     maps = {}
     inv, gen, _ = run(pipe, x, steps=a.steps, inv_steps=a.inv_steps, prompts=prompts, n_targets=len(a.target_prompt or [None]), attention_tokens=want_maps, maps_out=maps)
     torch.cuda.synchronize()
@@ -252,6 +287,12 @@ def main():
         for name, (m_inv, m_gen) in maps.items():
             print("saved", util.save_attention_maps(m_inv, f"{a.out}/sample/attn-{name}-inv.gif", size=a.size),
                   util.save_attention_maps(m_gen, f"{a.out}/sample/attn-{name}.gif", size=a.size))
+        if a.metrics:
+            import json
+            result = score(a.metrics, x, inv, gen, prompts, names)
+            Path(f"{a.out}/sample/metrics.json").write_text(json.dumps(result, indent=1))
+            print("metrics", json.dumps(result))
+            print("saved", f"{a.out}/sample/metrics.json")
 
 
 if __name__ == "__main__":

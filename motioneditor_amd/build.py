@@ -13,7 +13,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 OBJ = PKG / "csrc" / "_obj"
 LIB = PKG / "libmotioned.so"
-SOURCES = ["capi.hip", "gemm.hip", "attn.hip", "tattn.hip", "norm.hip", "eltwise.hip", "bwd.hip", "attn_bwd.hip", "train.hip", "plan.hip", "clip.hip", "image.hip", "tune.hip", "tattn_bwd_long.hip", "attn_probs.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "attn.hip", "tattn.hip", "norm.hip", "eltwise.hip", "bwd.hip", "attn_bwd.hip", "train.hip", "plan.hip", "clip.hip", "image.hip", "tune.hip", "tattn_bwd_long.hip", "attn_probs.hip", "clip_vision.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast"]
 # attn.hip: without nnan, every fmaxf on an MFMA result gets a canonicalising v_max_f32 in front of it (21 extra VALU per
 # 64-key tile in a kernel whose VALU time adds to its MFMA time); the kernel never produces or tests NaN / Inf.
@@ -40,7 +40,7 @@ def build_lib(force: bool = False, verbose: bool = True) -> Path:
     OBJ.mkdir(exist_ok=True)
     cc = hipcc()
     headers = [CSRC / "me_common.h", PKG.parent / "include" / "motioned.h", PKG.parent / "include" / "motioned_io.h", PKG.parent / "include" / "motioned_tune.h",
-               PKG.parent / "include" / "motioned_long.h", PKG.parent / "include" / "motioned_probe.h"]
+               PKG.parent / "include" / "motioned_long.h", PKG.parent / "include" / "motioned_probe.h", PKG.parent / "include" / "motioned_vision.h"]
 
     def one(src: str) -> Path:
         s, o = CSRC / src, OBJ / (Path(src).stem + ".o")

@@ -243,6 +243,18 @@ PROBE_SYMBOLS = {
     "me_attn_probs": (C.c_int, [C.POINTER(AttnProbsArgs), _vp]),
 }
 
+# every symbol include/motioned_vision.h declares (csrc/clip_vision.hip: the CLIP image encoder, the image processor and the cosine of the CLIP metrics;
+# scoring an edit is no part of a denoising step, so they stand outside its ABI as well)
+VISION_SYMBOLS = {
+    "me_attn_full_nmax": (C.c_int, []),
+    "me_attn_full": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp]),
+    "me_patch_rows": (C.c_int, [_vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "me_vit_tokens": (C.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "me_resample_u8": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    "me_crop_normalize": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "me_cosine_rows": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
+}
+
 _lib = None
 
 
@@ -263,7 +275,7 @@ def lib() -> C.CDLL:
         # and every launch would then fail with hipErrorNoDevice -- so make sure torch is loaded first.
         import torch  # noqa: F401
         L = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS, **TUNE_SYMBOLS, **LONG_SYMBOLS, **PROBE_SYMBOLS}.items():
+        for name, (res, args) in {**SYMBOLS, **IO_SYMBOLS, **TUNE_SYMBOLS, **LONG_SYMBOLS, **PROBE_SYMBOLS, **VISION_SYMBOLS}.items():
             fn = getattr(L, name)  # AttributeError if the .so does not export a declared symbol
             fn.restype, fn.argtypes = res, args
         if L.me_abi_version() != ABI_VERSION:

@@ -17,7 +17,8 @@ inference.py:141 and `torch.utils.data.DataLoader(ds, batch_size=1)` work unchan
     the file, the frame list is the sorted stems of `images/*`, every time.
   * A missing file, frames of unequal size and a clip with fewer frames than `n_sample_frames` raise errors that name the file and the value
     (the reference fails inside numpy / returns a short clip).
-  * `preprocess_img_embedding` raises NotImplementedError: the package has no image encoder.
+  * `preprocess_img_embedding` takes this package's `models.clip.CLIPImageProcessor` and `CLIPVisionModelWithProjection`; called without them it raises
+    NotImplementedError, as it did before the package had an image encoder.
 """
 from __future__ import annotations
 
@@ -82,8 +83,16 @@ class VideoDataset(Dataset):
         self.train_prompt = train_prompt
         self.device = device
 
+    @torch.no_grad()
     def preprocess_img_embedding(self, feature_extractor, image_encoder):
-        raise NotImplementedError("VideoDataset.preprocess_img_embedding: motioneditor_amd has no CLIP image encoder (dataset.py:76-82 is not built)")
+        """dataset.py:76-82: one CLIP image embedding [projection_dim] per frame of the folder, appended to `source_img_embeddings`.  The frames are decoded
+        with PIL (the reference's imageio gives the same RGB bytes) and go through processor and encoder -- this package's (models.clip) -- as one batch;
+        the encoder is batch-invariant bit for bit, so each row is what a call per frame gives.  Like __getitem__ it wants the frames of one size."""
+        if feature_extractor is None or image_encoder is None:
+            raise NotImplementedError("VideoDataset.preprocess_img_embedding: motioneditor_amd has no CLIP image encoder (dataset.py:76-82 is not built)")
+        frames = self._decode(self.video_path, self.frame_list, self.video_suffix, "RGB")         # uint8 [f, H, W, 3]: the whole folder in one batch
+        embeds = image_encoder(feature_extractor(frames).pixel_values).image_embeds              # fp32 [f, projection_dim]
+        self.source_img_embeddings.extend(embeds.unbind(0))
 
     def __len__(self):
         return 1

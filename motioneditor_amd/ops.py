@@ -1096,3 +1096,4 @@ def refresh_weights(table: RefreshTable) -> None:
 
 # The cross-attention probe (include/motioned_probe.h): ops.attention_probs, written in probe.py
 from .probe import attention_probs  # noqa: E402,F401
+from .vision import attention_full, cosine_rows, crop_normalize, patch_rows, resample_u8, vit_tokens  # noqa: E402,F401
